@@ -13,7 +13,21 @@ timed region: the x1.163842 icosahedral mesh (mpasdyn.mesh) with its one-time
 precompute uploaded from the host, and the 3-D state filled on the device by the
 seeded generator (data: synthetic, seed 20211015).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, K timed steps,
+the result line (metric, value, ms_per_step, the configuration, the step's algorithmic
+bytes).  --full adds, as separate runs of their own, the legs described below: the live
+HBM traffic passes (--traffic), the per-task device times with the roofline, and the
+cpu_baseline (--no-cpu-baseline).  --dump-outputs DIR writes, after the timed steps, what
+the last timed step left in the context -- every fp64 field a task writes (distribution U
+of include/mpas_fields.def) -- as DIR/<field>.npy in float64: all rows of a field up to
+OUT_ROWS, else a fixed seeded sample of OUT_ROWS rows per entity (64 MB at most in all).
+The inputs are the same bits in every run with the same arguments.  No filling of the
+state is stepped more than REFILL_STEPS times (refill_inputs: the reference semantics let
+the acoustic perturbations grow without bound on the synthetic state): a longer run fills
+the state again between two timed runs of steps, outside the clocks, with one untimed step
+after it, so the outputs are finite for any K.
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the ranks are
 the launcher's and WORLD_SIZE must equal N; without it bench.py starts the N rank
@@ -31,7 +45,7 @@ north-star kernel; its rk_step 0 and rk_step > 0 launches are one Regent task),
 achieved = its algorithmic bytes per step (mpasdyn/roofline.py) / its
 device time per step (HIP events on the task stream), i.e. the launch-weighted average;
 traffic = its HBM bytes per launch from rocprofv3 FETCH_SIZE and WRITE_SIZE passes over
-this same workload, run by this script before it touches the GPU (--traffic auto).
+this same workload, run by this script before it touches the GPU (--full, --traffic auto).
 
 Prints ONE JSON line on rank 0.
 """
@@ -120,6 +134,21 @@ def upload_inputs(ctx, st):
     ctx.fill_synthetic(SEED)  # all DIST U fields, on the device
     names = [f.name for f in FIELDS if f.dist == "M" or f.kind == "ZV"]
     ctx.upload(st, names=names)  # mesh data + one-time precompute + vertical grid
+    ctx.sync()
+
+
+REFILL_STEPS = 64
+
+
+def refill_inputs(ctx, st):
+    """the inputs of upload_inputs again, on the device.  The reference semantics carry the
+    acoustic perturbations (rho_pp, rtheta_pp, rw_p, ru_p) from step to step and nothing damps
+    them on the synthetic state: they grow about 40-fold per step and leave fp64 near 190
+    steps.  So a run never makes more than REFILL_STEPS steps on one filling; the step's work
+    does not depend on the values, and its last outputs stay finite for any --steps."""
+    from mpasdyn.registry import FIELDS
+    ctx.fill_synthetic(SEED)  # (also the vertical grid's fields: uploaded again)
+    ctx.upload(st, names=[f.name for f in FIELDS if f.kind == "ZV"])
     ctx.sync()
 
 
@@ -253,6 +282,39 @@ def dump_rows(path, ctx, st, gids, steps, extra):
     for k, v in extra.items():
         out[k] = np.asarray(v)
     np.savez(path, **out)
+
+
+OUT_ROWS = 512  # --dump-outputs: rows per entity (cells, edges, vertices)
+OUT_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, ctx, st):
+    """--dump-outputs: every fp64 field the tasks write (dist U with an entity), as the last
+    timed step left it, one float64 .npy per field.  A field of more than OUT_ROWS rows is
+    cut to a sample of OUT_ROWS rows, the same sorted rows for every field of an entity,
+    drawn once per entity by a generator seeded with SEED -- so two builds write the same
+    rows of the same inputs."""
+    from mpasdyn.registry import FIELDS
+    from mpasdyn.state import HostState
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    n_of = {"cell": st.nCells, "edge": st.nEdges, "vertex": st.nVertices}
+    rows = {k: np.arange(n) if n <= OUT_ROWS else np.sort(rng.choice(n, size=OUT_ROWS, replace=False))
+            for k, n in n_of.items()}
+    host = HostState(*st.dims(), names=[])
+    bufs, total = {}, 0  # (one host buffer per field shape: the fields are downloaded whole)
+    for f in FIELDS:
+        if f.entity is None or f.dtype != np.float64 or f.dist != "U":
+            continue
+        shape = host.shape_of(f)
+        if shape not in bufs:
+            bufs[shape] = np.zeros(shape, dtype=np.float64)
+        host.arrays = {f.name: bufs[shape]}
+        ctx.download(host)
+        a = np.ascontiguousarray(bufs[shape][rows[f.entity]])
+        total += a.nbytes
+        assert total <= OUT_MAX_BYTES, f"--dump-outputs: more than {OUT_MAX_BYTES} bytes at {f.name}"
+        np.save(os.path.join(path, f.name + ".npy"), a)
 
 
 def spawn_ranks(n, argv):
@@ -487,6 +549,43 @@ def frac_excl_copy(t):
     return round(b / (t["ms_per_step"] * 1e-3) / HBM_PEAK_GBS, 4)
 
 
+def task_legs(ctx, dt, n_prof, work_dims, physics, smls, traffic_by, traffic_note):
+    """--full: n_prof further steps with the library's per-task timing on; returns the
+    roofline record of the north-star task and the per-task table"""
+    from mpasdyn import tasks as T
+    # per-task device times (HIP events bracketing every task on the task stream)
+    ctx.timing(True)
+    ctx.timing_reset()
+    for _ in range(n_prof):
+        T.atm_srk3(ctx, dt, 1)
+    ctx.sync()
+    rep = ctx.timing_report()
+    ctx.timing(False)
+    tasks_out = task_table(rep, work_dims, n_prof, physics, ddx=smls)
+    if traffic_by:
+        for name, t in tasks_out.items():
+            keys = [k for k in traffic_by if k.split("[")[0] == name]
+            if keys:  # SURVEY §8.5 metric 2: measured (FETCH + WRITE) bytes over this run's device time
+                b = sum(sum(traffic_by[k]) for k in keys)
+                t["hbm_GB_measured_per_step"] = round(b / 1e9, 4)
+                t["hbm_frac_measured"] = round(b / (t["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    dom = max(tasks_out, key=lambda k: tasks_out[k]["ms_per_step"])
+    ns = tasks_out[NORTH_STAR]
+    traffic = None
+    if "hbm_GB_measured_per_step" in ns:
+        traffic = round(ns["hbm_GB_measured_per_step"] / ns["launches_per_step"], 4)
+    roof = {"bound": "hbm", "kernel": NORTH_STAR, "achieved": ns["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": ns["frac"], "traffic": traffic, "traffic_unit": "GB/launch",
+            "traffic_over_b_alg": round(traffic / ns["b_alg_GB"], 3) if traffic else None,
+            "traffic_frac": ns.get("hbm_frac_measured"), "traffic_source": traffic_note,
+            "b_alg_per_launch_GB": ns["b_alg_GB"], "avg_launch_ms": ns["avg_ms"],
+            "launches_per_step": ns["launches_per_step"], "ms_per_step": ns["ms_per_step"],
+            "frac_excl_fusecopy": frac_excl_copy(ns), "variants": ns.get("variants"), "dominant_task": dom,
+            "note": "achieved = B_alg per step / device time per step of the task (launch-weighted average of its "
+                    "rk_step 0 and rk_step > 0 launches); frac = achieved / peak"}
+    return roof, tasks_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -495,6 +594,12 @@ def main():
     ap.add_argument("--ncells", type=int, default=163842)
     ap.add_argument("--levels", type=int, default=56)
     ap.add_argument("--exact", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: the live traffic passes (--traffic), the "
+                         "per-task device times with the roofline, the cpu_baseline (--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the fields of the last timed step as DIR/<field>.npy "
+                         "(float64; a fixed seeded sample of the rows of a large field)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of oracle steps in the cpu_baseline leg")
     ap.add_argument("--traffic", choices=["auto", "off"], default="auto",
@@ -523,6 +628,9 @@ def main():
         args.physics = 1
     if args.pmc_child:
         return pmc_child(args)
+    if args.dump_outputs and args.gpus != 1:
+        print("bench.py: --dump-outputs writes one context's fields: --gpus 1", file=sys.stderr)
+        return 2
 
     # ranks: the launcher's (torch.distributed.run) or our own children
     if "WORLD_SIZE" in os.environ:
@@ -553,7 +661,7 @@ def main():
 
     # live traffic first: the profiled children start before this process touches the GPU
     traffic_by, traffic_note = None, "off"
-    if args.traffic == "auto" and world == 1 and rank == 0 and not args.decompose:
+    if args.full and args.traffic == "auto" and world == 1 and rank == 0 and not args.decompose:
         traffic_by, traffic_note = measure_traffic(args)
 
     # Libraries print banners on stdout from C (RCCL's version lines at communicator
@@ -621,8 +729,20 @@ def main():
 
     # (the first step makes the first halo exchanges: bounded like the communicator set-up)
     wd = Watchdog(args.init_timeout, "the first RK3 step (its halo exchanges)", rank) if decomposed else None
+    age, refills = 0, 0  # steps since the state was filled; refills (one untimed step each)
+
+    def refill():
+        nonlocal age, refills
+        refill_inputs(ctx, st)
+        T.atm_srk3(ctx, dt, 1)  # (untimed: the upload dropped the captured step, this one captures it again)
+        ctx.sync()
+        age, refills = 1, refills + 1
+
     for i in range(args.warmup):
+        if age >= REFILL_STEPS:
+            refill()
         T.atm_srk3(ctx, dt, 1)
+        age += 1
         if i == 0 and wd is not None:
             ctx.sync()
             wd.cancel()
@@ -633,25 +753,36 @@ def main():
         if rv is not None:
             rv.barrier()
 
-    # K timed steps, bracketed by barrier + device synchronisation on both sides; one HIP
-    # event between consecutive steps on the task stream gives the per-step device times
-    # (the median step), the wall clock the whole region
-    evs = [hip.event() for _ in range(args.steps + 1)]
-    barrier()
-    hip.device_sync()
-    t0 = time.perf_counter()
-    hip.record(evs[0], stream)
-    for i in range(args.steps):
-        T.atm_srk3(ctx, dt, 1)
-        hip.record(evs[i + 1], stream)
-        if wd is not None:  # (no warm-up: the first timed step made the first exchanges)
-            ctx.sync()
-            wd.cancel()
-            wd = None
-    ctx.sync()
-    hip.device_sync()
-    barrier()
+    # K timed steps in runs of at most REFILL_STEPS since the state was filled (one run when
+    # W + K <= REFILL_STEPS), each run bracketed by barrier + device synchronisation on both
+    # sides; one HIP event between consecutive steps on the task stream gives the per-step
+    # device times (the median step), the wall clock the runs as a whole.  Between
+    # two runs, outside both clocks, the state is filled again (refill_inputs).
+    pairs, t_wall, done = [], 0.0, 0
+    while done < args.steps:
+        if age >= REFILL_STEPS:
+            refill()
+        nb = min(args.steps - done, REFILL_STEPS - age)
+        evs = [hip.event() for _ in range(nb + 1)]
+        barrier()
+        hip.device_sync()
+        t0 = time.perf_counter()
+        hip.record(evs[0], stream)
+        for i in range(nb):
+            T.atm_srk3(ctx, dt, 1)
+            hip.record(evs[i + 1], stream)
+            if wd is not None:  # (no warm-up: the first timed step made the first exchanges)
+                ctx.sync()
+                wd.cancel()
+                wd = None
+        ctx.sync()
+        hip.device_sync()
+        barrier()
+        t_wall += time.perf_counter() - t0
+        pairs += list(zip(evs[:-1], evs[1:]))
+        done, age = done + nb, age + nb
     if args.dump:  # (after the timed steps, before the per-task timing steps)
+        t0 = time.perf_counter()
         os.makedirs(args.dump, exist_ok=True)
         if decomposed:
             gids = {k: dec.owned[rank][k] for k in ("cell", "edge", "vertex")}
@@ -659,51 +790,26 @@ def main():
         else:
             gids = {"cell": np.arange(m.nCells), "edge": np.arange(m.nEdges), "vertex": np.arange(m.nVertices)}
             ex = 0
-        dump_rows(os.path.join(args.dump, f"rank{rank}.npz"), ctx, st, gids, args.warmup + args.steps,
+        dump_rows(os.path.join(args.dump, f"rank{rank}.npz"), ctx, st, gids, args.warmup + args.steps + refills,
                   {"exchanges": ex, "world": world})
         barrier()
-    t_wall = time.perf_counter() - t0
-    step_ms = [hip.elapsed_ms(evs[i], evs[i + 1]) for i in range(args.steps)]
+        t_wall += time.perf_counter() - t0  # (as before the runs: the wall clock spans the fingerprints)
+    step_ms = [hip.elapsed_ms(e0, e1) for e0, e1 in pairs]
     ms_median = statistics.median(step_ms)
     ms_mean = max(t_wall * 1000.0, sum(step_ms)) / args.steps
     if rv is not None:  # the slowest rank sets the job's step time
         ms_median = rv.allreduce_max(ms_median)
         ms_mean = rv.allreduce_max(ms_mean)
     ms_step = ms_median
+    if args.dump_outputs:  # (the state the last timed step left, before any further step)
+        dump_outputs(args.dump_outputs, ctx, st)
 
-    # per-task device times (HIP events bracketing every task on the task stream)
-    ctx.timing(True)
-    ctx.timing_reset()
-    n_prof = 2
-    for _ in range(n_prof):
-        T.atm_srk3(ctx, dt, 1)
-    ctx.sync()
-    rep = ctx.timing_report()
-    ctx.timing(False)
     smls = (bool(ctx.get_option("fusedamp_active")) and bool(ctx.get_option("fusesml")) and
             bool(ctx.get_option("smlsum")) and not args.exact and not args.physics)
-    tasks_out = task_table(rep, work_dims, n_prof, args.physics, ddx=smls)
-    if traffic_by:
-        for name, t in tasks_out.items():
-            keys = [k for k in traffic_by if k.split("[")[0] == name]
-            if keys:  # SURVEY §8.5 metric 2: measured (FETCH + WRITE) bytes over this run's device time
-                b = sum(sum(traffic_by[k]) for k in keys)
-                t["hbm_GB_measured_per_step"] = round(b / 1e9, 4)
-                t["hbm_frac_measured"] = round(b / (t["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    dom = max(tasks_out, key=lambda k: tasks_out[k]["ms_per_step"])
-    ns = tasks_out[NORTH_STAR]
-    traffic = None
-    if "hbm_GB_measured_per_step" in ns:
-        traffic = round(ns["hbm_GB_measured_per_step"] / ns["launches_per_step"], 4)
-    roof = {"bound": "hbm", "kernel": NORTH_STAR, "achieved": ns["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": ns["frac"], "traffic": traffic, "traffic_unit": "GB/launch",
-            "traffic_over_b_alg": round(traffic / ns["b_alg_GB"], 3) if traffic else None,
-            "traffic_frac": ns.get("hbm_frac_measured"), "traffic_source": traffic_note,
-            "b_alg_per_launch_GB": ns["b_alg_GB"], "avg_launch_ms": ns["avg_ms"],
-            "launches_per_step": ns["launches_per_step"], "ms_per_step": ns["ms_per_step"],
-            "frac_excl_fusecopy": frac_excl_copy(ns), "variants": ns.get("variants"), "dominant_task": dom,
-            "note": "achieved = B_alg per step / device time per step of the task (launch-weighted average of its "
-                    "rk_step 0 and rk_step > 0 launches); frac = achieved / peak"}
+    n_prof, roof, tasks_out = 0, None, None
+    if args.full:
+        n_prof = 2
+        roof, tasks_out = task_legs(ctx, dt, n_prof, work_dims, args.physics, smls, traffic_by, traffic_note)
     fused = bool(ctx.get_option("fusedamp_active"))
     fsetup = bool(ctx.get_option("fusesetup"))
     fsml = fused and bool(ctx.get_option("fusesml")) and not args.physics
@@ -723,8 +829,8 @@ def main():
     value = (1 if decomposed else world) * ncells / (ms_step * 1e-3) / 1e6
     if decomposed:
         ex, fl = lib.halo_stats(ctx)
-        halo_info["exchanges_per_step"] = round(ex / (args.warmup + args.steps + n_prof), 2)
-        halo_info["fields_per_step"] = round(fl / (args.warmup + args.steps + n_prof), 2)
+        halo_info["exchanges_per_step"] = round(ex / (args.warmup + args.steps + n_prof + refills), 2)
+        halo_info["fields_per_step"] = round(fl / (args.warmup + args.steps + n_prof + refills), 2)
     out = {"metric": METRIC, "value": round(value, 3), "unit": "Mcell-columns/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
            "ms_per_step_stat": f"median of {args.steps} per-step HIP-event times on the task stream, max over ranks "
@@ -743,11 +849,14 @@ def main():
                       "graph": ctx.get_option("graph") if not decomposed else 0, "fusedamp": int(fused), "fusesetup": int(fsetup), "fusecopy": int(fcopy), "smlsum": int(smls),
                       "fusesml": int(fsml), "defer4": int(d4), "ntu": int(ntu), "mdamp": int(mdamp), "trsave": int(trsave), "mru": int(mru), "msml": int(msml), "tmedge": int(fused and bool(ctx.get_option("tmedge"))),
                       "hfuse": int(bool(ctx.get_option("hfuse_active")))},
-           "step_b_alg_GB": round(b_step / 1e9, 3), "step_achieved_GBs": round(step_gbs, 1),
-           "roofline": roof, "tasks": tasks_out}
+           "step_b_alg_GB": round(b_step / 1e9, 3), "step_achieved_GBs": round(step_gbs, 1)}
+    if args.full:
+        out["roofline"], out["tasks"] = roof, tasks_out
     if halo_info:
         out["halo"] = halo_info
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:
+        pass  # (a plain run: no cpu_baseline leg, no key)
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
         # all the host cores this process may use: the OMP_NUM_THREADS pin when the
         # environment sets one (the GPU box pins 16, its CPU share per GPU), else nproc
         pin = os.environ.get("OMP_NUM_THREADS")

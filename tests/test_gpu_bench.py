@@ -13,10 +13,10 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
         "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
 
 
-def run_bench(*args, timeout=110):
+def run_bench(*args, timeout=110, full=True):
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--traffic", "off", *args], capture_output=True, text=True,
-                       timeout=timeout, cwd=REPO)
+                        *(["--full", "--no-cpu-baseline", "--traffic", "off"] if full else []), *args],
+                       capture_output=True, text=True, timeout=timeout, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, f"stdout must be ONE JSON line, got {len(lines)}: {p.stdout[:500]}"
@@ -38,6 +38,50 @@ def test_bench_line(mode):
         assert d["halo"]["exchanges_per_step"] > 0 and d["halo"]["ghost_frac"] == [0.0, 0.0, 0.0]
     else:
         assert d["scaling"] == "weak" and d["config"]["parallelism"] == "single-gpu"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain run (no --full) prints the headline keys without the legs that take runs of
+    their own, and --dump-outputs writes the last timed step's fields as float64 .npy, the
+    same bits in two runs (x1.2562 x 56 has more rows than the sample: 512 per entity)"""
+    import numpy as np
+    from mpasdyn.registry import FIELDS
+    ds = [run_bench("--ncells", "2562", "--dump-outputs", str(tmp_path / k), full=False) for k in "ab"]
+    for d in ds:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps"} <= set(d)
+        assert not {"roofline", "tasks", "cpu_baseline"} & set(d)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "Mcell-columns/s" and d["dtype"] == "f64"
+        assert abs(d["value"] - 2562 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * d["value"]
+    names = sorted(f.name for f in FIELDS if f.entity is not None and f.dtype == np.float64 and f.dist == "U")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "b")) == [n + ".npy" for n in names]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float64 and a.shape[0] == 512 and a.shape == b.shape
+        assert np.array_equal(a, b, equal_nan=True), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    theta = np.load(tmp_path / "a" / "theta_m.npy")
+    fin = theta[np.isfinite(theta)]
+    assert fin.size and fin.std() > 0  # (a filled field, not an empty buffer)
+
+
+@pytest.mark.gpu
+def test_bench_outputs_finite_in_a_long_run(tmp_path):
+    """the headline semantics let the acoustic perturbations grow about 40-fold per step (fp64
+    ends near 190 steps of one filling): bench.py fills the state again every 64 steps, outside
+    the clocks, so --steps really sets the timed steps and the last step's fields are finite"""
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "260", "--warmup", "70",
+                        "--ncells", "2562", "--dump-outputs", str(tmp_path / "o")], capture_output=True, text=True,
+                       timeout=110, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip())
+    assert d["steps"] == 260 and d["warmup"] == 70 and d["ms_per_step"] > 0
+    assert "median of 260 " in d["ms_per_step_stat"]
+    bad = [f for f in sorted(os.listdir(tmp_path / "o")) if not np.isfinite(np.load(tmp_path / "o" / f)).all()]
+    assert not bad, bad
 
 
 @pytest.mark.gpu
@@ -68,7 +112,7 @@ def test_bench_roofline_is_dyn_tend_with_live_traffic():
     """the roofline names the north-star task (dyn_tend: rk0 + 2 rk>0 launches per step),
     and its traffic comes from rocprofv3 FETCH_SIZE / WRITE_SIZE passes of the same
     workload run by bench.py itself (x1.40962 keeps the passes short)"""
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--ncells", "40962"], capture_output=True, text=True, timeout=300,
                        cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -13,7 +13,7 @@
 #   LIBS="abl/old.so ..."          the other library builds of the "libab" recipe (MPAS_LIB)
 # Recipes:
 #   tests   the listed GPU tests, verbose          suite   the whole GPU suite + smoke()
-#   bench   one bench.py JSON line                 trace   rocprofv3 kernel trace + stats of bench.py
+#   bench   one bench.py --full JSON line          trace   rocprofv3 kernel trace + stats of bench.py
 #   pmc     FETCH / WRITE / TCC hit-miss passes (one counter group per run) + per-kernel table
 #   abstep  tools/abstep.py whole-step A/B (AB)    kbench  tools/kbench.py per-task A/B (AB)
 #   ranksim tools/rank_sim.py, overlap 0/1 (RS_ARGS)
@@ -34,7 +34,7 @@ for R in "$@"; do
       timeout -k 10 1000 $PYT -q tests > "$OUT/gpu_tests.log" 2>&1
       timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
     bench)
-      timeout -k 10 500 python3 bench.py $BA > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+      timeout -k 10 500 python3 bench.py --full $BA > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     trace)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o kt --output-format csv -- \
         python3 bench.py $BA --no-cpu-baseline --traffic off > "$OUT/trace.log" 2>&1 ;;
