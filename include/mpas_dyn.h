@@ -125,7 +125,13 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * Default 0: the reference's semantics.
  * "transport" = 1 (needs "physics" >= 1) makes mpas_atm_srk3 copy scalars
  * to scalars_old first and run mpas_atm_advance_scalars_mono(dt) after the last stage's
- * recover, before atm_rk_dynamics_substep_finish.  Default 0.  "trorder" (speed only)
+ * recover, before atm_rk_dynamics_substep_finish.  "transport" = 2 (the same need) integrates
+ * the scalars with MPAS-A's three-stage RK3 instead: after the same copy and at the same place,
+ * mpas_atm_advance_scalars(dt/3), mpas_atm_advance_scalars(dt/2), then
+ * mpas_atm_advance_scalars_mono_rk(dt), every stage with the step's ruAvg, wwAvg and
+ * rho_zz_old_split (third order in time where the limiter is idle; the copy is always the
+ * separate one; MPAS_ENOTSUP with "trtile", "tredge", "trsu" or "trepw" = 2).  Any other value:
+ * MPAS_EINVAL.  Default 0.  "trorder" (speed only)
  * orders the transport's column slots: 0 entity-major, 1 pair-major, R >= 2 pair-major
  * within runs of R consecutive entities, one run per XCD (default 64); "trorder_e" the same
  * for the transport's edge kernel alone (0, the default: trorder's).  "trsu" = 1 (speed only; measured
@@ -268,6 +274,24 @@ int mpas_atm_core_init(mpas_ctx* ctx);
  *       Statement order: oracle/mpas_oracle.c ora_mpas_advance_scalars_mono.  Decomposed
  *       contexts exchange scalars_old and the scratch on their ghosts like every task. */
 int mpas_atm_advance_scalars_mono(mpas_ctx* ctx, double dt);
+/* One unlimited stage of MPAS-A's atm_advance_scalars (the first two stages of its RK3 scalar
+ *       transport; no reference entry point, Q26).  With s_old = scalars_old, s_flux = scalars as
+ *       found, ro = rho_zz_old_split, u = ruAvg, w = wwAvg (interfaces 0 and nVertLevels carry no
+ *       flux and are not read), sg = +1 where the cell is cellsOnEdge(e,0), else -1:
+ *         H(e,k)  = u sum_j (adv_coefs_j + sign(u) adv_coefs_3rd_j) s_flux(advCell_j,k)
+ *         V(c,kk) = the interface high-order flux of mpas_atm_advance_scalars_mono on s_flux
+ *         D(c,k)  = invAreaCell sum_e sg dvEdge u + rdzw(k) (w(k+1) - w(k))
+ *         rho_int = ro - dt D                      (MPAS's advance_density: a constant stays constant)
+ *         scalars = (s_old ro - dt (invAreaCell sum_e sg H + rdzw(k) (V(k+1) - V(k)))) / rho_int
+ *       Writes scalars (levels 0..nVertLevels-1) only; rho_zz is neither read nor written.
+ *       MPAS_ENOTSUP with "trtile", "tredge", "trsu" or "trepw" = 2 set. */
+int mpas_atm_advance_scalars(mpas_ctx* ctx, double dt);
+/* mpas_atm_advance_scalars_mono with its two high-order fluxes (the edge sum over the adv list and
+ *       the interface flux) evaluated on scalars as found -- the previous stage's estimate -- and
+ *       everything else (upwind fluxes, bounds, the upwind update, R+ / R-) on scalars_old: the
+ *       last stage of the RK3 scalar transport.  Bit-identical to mpas_atm_advance_scalars_mono
+ *       when scalars equals scalars_old on entry.  MPAS_ENOTSUP as above. */
+int mpas_atm_advance_scalars_mono_rk(mpas_ctx* ctx, double dt);
 /* rk_timestep.rg:29 summarize_timestep(cr, er, config_print_detailed_minmax_vel,
  *       config_print_global_minmax_vel, config_print_global_minmax_sca): the values the
  *       reference prints, into out[31] (host memory; the call synchronises):

@@ -21,6 +21,12 @@
 // entity read the same connectivity, mass fluxes and densities (one HBM fetch, then L2
 // hits).  One wavefront per column pair at 57 levels (LP = 64); the vertical neighbours
 // are lane shuffles.
+//
+// The RK3 transport (option "transport" = 2, MPAS-A with dynamics and transport split) adds
+// two tasks in the same idiom: the unlimited stage (k_tra_edge, k_tra_cell; below) and the
+// monotonic task with its two high-order fluxes taken on scalars, the stage before, instead
+// of scalars_old (k_trk_edge / k_trk_bounds / k_trk_update: the RK forms of the three
+// kernels above, the same bodies).
 #include "mpas_dev.h"
 #include "mpas_halo.h"
 
@@ -146,13 +152,22 @@ __device__ __forceinline__ double& sat(Px x, const double* f, int ent, int i, in
     return *(double*)MPAS_CHK(f, (double*)(pcol<LP>(x, f, ent, i) + k) + (i & 1), 8);
 }
 
-// interface k of a column: upwind (lo) and antidiffusive (A) vertical flux of the lane's
-// level; no flux through interfaces 0 and L
+// interface k of a column: the high-order vertical flux of the lane's level (flux3 between
+// the second and the last-but-one interface, second order at interfaces 1 and L-1)
 template <int LP>
-__device__ __forceinline__ void tr_vflux(double s, double w, int k, int L, double fzm, double fzp, double& lo,
-                                         double& A) {
+__device__ __forceinline__ double tr_vhi(double s, double w, int k, int L, double fzm, double fzp) {
     const double sm1 = lvl_dn<LP>(s, k), sm2 = lvl_dn2<LP>(s, k), sp1 = lvl_up<LP>(s, k);
-    const double hi = (k >= 2 && k <= L - 2) ? tr_flux3(sm2, sm1, s, sp1, w) : w * (fzm * s + fzp * sm1);
+    return (k >= 2 && k <= L - 2) ? tr_flux3(sm2, sm1, s, sp1, w) : w * (fzm * s + fzp * sm1);
+}
+// interface k of a column: upwind (lo) and antidiffusive (A) vertical flux of the lane's
+// level; no flux through interfaces 0 and L.  The high-order flux is taken from sf, the
+// upwind flux from s (the monotonic task: sf is s; its RK form: the previous stage's estimate)
+template <int LP>
+__device__ __forceinline__ void tr_vflux(double s, double sf, double w, int k, int L, double fzm, double fzp,
+                                         double& lo, double& A) {
+    const double sm1 = lvl_dn<LP>(s, k);
+    const double fm1 = lvl_dn<LP>(sf, k), fm2 = lvl_dn2<LP>(sf, k), fp1 = lvl_up<LP>(sf, k);
+    const double hi = (k >= 2 && k <= L - 2) ? tr_flux3(fm2, fm1, sf, fp1, w) : w * (fzm * sf + fzp * fm1);
     const double l = fmax(w, 0.0) * sm1 + fmin(w, 0.0) * s;
     const bool in = k >= 1 && k <= L - 1;
     lo = in ? l : 0.0;
@@ -222,8 +237,10 @@ __global__ __launch_bounds__(256) void k_tr_edge_n(DevState S) {
     }
 }
 
-template <int LP>
-__global__ __launch_bounds__(256) void k_tr_edge(DevState S) {
+// RK (mpas_atm_advance_scalars_mono_rk): the high-order flux from scalars, the previous
+// stage's estimate; the upwind flux from scalars_old
+template <int LP, bool RK>
+__device__ __forceinline__ void tr_edge(const DevState& S) {
     int e, p;
     tr_slot<LP>(S, KE, e, p);
     const int L = S.L, k = (int)(threadIdx.x % LP);
@@ -239,14 +256,15 @@ __global__ __launch_bounds__(256) void k_tr_edge(DevState S) {
     row_ld(fd(S, F_adv_coefs_3rd) + (size_t)e * 15, ac3);
     const double dv = fd(S, F_dvEdge)[e];
     const double* so = fd(S, S.trsave ? F_scalars : F_scalars_old);  // (trsave: scalars holds the old values)
+    const double* sf = RK ? fd(S, F_scalars) : so;
     const double u = colk(fd(S, F_ruAvg), e);
     double xa[AF], xb[AF], s1a, s1b, s2a, s2b;
 #pragma unroll
-    for (int j = 0; j < AF; j++) ld2<LP>(XP, so, adv[j], p, k, xa[j], xb[j]);
+    for (int j = 0; j < AF; j++) ld2<LP>(XP, sf, adv[j], p, k, xa[j], xb[j]);
     // the upwind flux's two cells are normally advCellsForEdge(0) and (1) (MPAS's list
     // construction): take their columns from the list; gather them only where they are not
-    // (wave-uniform branch, the same column either way)
-    if (na >= 2 && adv[0] == c1 && adv[1] == c2) {
+    // (wave-uniform branch, the same column either way; RK: the list's columns are another field's)
+    if (!RK && na >= 2 && adv[0] == c1 && adv[1] == c2) {
         s1a = xa[0], s1b = xb[0], s2a = xa[1], s2b = xb[1];
     } else {
         ld2<LP>(XP, so, c1, p, k, s1a, s1b);
@@ -264,13 +282,21 @@ __global__ __launch_bounds__(256) void k_tr_edge(DevState S) {
         const int cj = fi(S, F_advCellsForEdge)[(size_t)e * 15 + j];
         const double wgt = fd(S, F_adv_coefs)[(size_t)e * 15 + j] + sgn * fd(S, F_adv_coefs_3rd)[(size_t)e * 15 + j];
         double ya, yb;
-        ld2<LP>(XP, so, cj, p, k, ya, yb);
+        ld2<LP>(XP, sf, cj, p, k, ya, yb);
         acca = acca + wgt * ya;
         accb = accb + wgt * yb;
     }
     const double loa = dv * (fmax(u, 0.0) * s1a + fmin(u, 0.0) * s2a);
     const double lob = dv * (fmax(u, 0.0) * s1b + fmin(u, 0.0) * s2b);
     st2<LP>(XS, fw(S, X_Ah), e, p, k, PADW(u * acca - loa), PADW(u * accb - lob));
+}
+template <int LP>
+__global__ __launch_bounds__(256) void k_tr_edge(DevState S) {
+    tr_edge<LP, false>(S);
+}
+template <int LP>
+__global__ __launch_bounds__(256) void k_trk_edge(DevState S) {
+    tr_edge<LP, true>(S);
 }
 
 // k_tr_edge with the scalars_old columns staged in LDS (option "tredge", opt-in: measured
@@ -418,7 +444,7 @@ __device__ __forceinline__ void tr_bound_slot(bool on, int s1f, double dv, doubl
 
 // the rest of k_tr_bounds for one scalar: vertical bounds and fluxes, su, R+ / R-
 template <int LP>
-__device__ __forceinline__ void tr_bound_fin(TrAcc& r, double s, double w, double r_o, double r_n, double invA,
+__device__ __forceinline__ void tr_bound_fin(TrAcc& r, double s, double sf, double w, double r_o, double r_n, double invA,
                                              double rdzw, double fzm, double fzp, double dt, int k, int L,
                                              double& Rp, double& Rm, double& su) {
     const double sm1 = lvl_dn<LP>(s, k), sp1 = lvl_up<LP>(s, k);
@@ -427,7 +453,7 @@ __device__ __forceinline__ void tr_bound_fin(TrAcc& r, double s, double w, doubl
     r.smax = k < L - 1 ? fmax(r.smax, sp1) : r.smax;
     r.smin = k < L - 1 ? fmin(r.smin, sp1) : r.smin;
     double lob, Ab;
-    tr_vflux<LP>(s, w, k, L, fzm, fzp, lob, Ab);
+    tr_vflux<LP>(s, sf, w, k, L, fzm, fzp, lob, Ab);
     const double lot = lvl_up<LP>(lob, k), At = lvl_up<LP>(Ab, k);
     su = (s * r_o - dt * (r.hlo * invA + (lot - lob) * rdzw)) / r_n;
     r.smax = fmax(r.smax, su);
@@ -440,8 +466,10 @@ __device__ __forceinline__ void tr_bound_fin(TrAcc& r, double s, double w, doubl
 }
 
 // SU (option "trsu"): su is not stored; k_tr_update forms it again from the same values
-template <int LP, bool SELF, bool SU>
-__global__ __launch_bounds__(256) void k_tr_bounds(DevState S, double dt) {
+// RK (mpas_atm_advance_scalars_mono_rk): the interface high-order flux from the cell's scalars
+// column, the previous stage's estimate; every other value from scalars_old
+template <int LP, bool SELF, bool SU, bool RK>
+__device__ __forceinline__ void tr_bounds(const DevState& S, double dt) {
     int c, p;
     tr_slot<LP>(S, KC, c, p);
     const int L = S.L, k = (int)(threadIdx.x % LP);
@@ -466,6 +494,8 @@ __global__ __launch_bounds__(256) void k_tr_bounds(DevState S, double dt) {
     } else {
         ld2<LP>(XP, so, c, p, k, sa, sb);
     }
+    double sfa = sa, sfb = sb;
+    if constexpr (RK) ld2<LP>(XP, fd(S, F_scalars), c, p, k, sfa, sfb);
     const double w = colk(fd(S, F_wwAvg), c), r_o = colk(fd(S, F_rho_zz_old_split), c), r_n = colk(fd(S, F_rho_zz), c);
     double u_[NF], x1a[NF], x2a[NF], x1b[NF], x2b[NF], Aa[NF], Ab[NF];
 #pragma unroll
@@ -505,8 +535,8 @@ __global__ __launch_bounds__(256) void k_tr_bounds(DevState S, double dt) {
         tr_bound_slot(true, s1f, dv, u, y1b, y2b, Bb, rb);
     }
     double Rpa, Rma, sua, Rpb, Rmb, sub;
-    tr_bound_fin<LP>(ra, sa, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rpa, Rma, sua);
-    tr_bound_fin<LP>(rb, sb, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rpb, Rmb, sub);
+    tr_bound_fin<LP>(ra, sa, sfa, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rpa, Rma, sua);
+    tr_bound_fin<LP>(rb, sb, sfb, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rpb, Rmb, sub);
     // level L and the padding levels of the scratch are never read
     st2<LP>(XS, fw(S, X_Rp), c, p, k, Rpa, Rpb);
     st2<LP>(XS, fw(S, X_Rm), c, p, k, Rma, Rmb);
@@ -520,14 +550,22 @@ __global__ __launch_bounds__(256) void k_tr_bounds(DevState S, double dt) {
         }
     }
 }
+template <int LP, bool SELF, bool SU>
+__global__ __launch_bounds__(256) void k_tr_bounds(DevState S, double dt) {
+    tr_bounds<LP, SELF, SU, false>(S, dt);
+}
+template <int LP, bool SELF>
+__global__ __launch_bounds__(256) void k_trk_bounds(DevState S, double dt) {
+    tr_bounds<LP, SELF, false, true>(S, dt);
+}
 
 // the limited update of one scalar
 template <int LP>
-__device__ __forceinline__ double tr_update_fin(double hc, double s, double w, double su, double rp, double rm,
+__device__ __forceinline__ double tr_update_fin(double hc, double s, double sf, double w, double su, double rp, double rm,
                                                 double r_n, double invA, double rdzw, double fzm, double fzp,
                                                 double dt, int k, int L) {
     double lo, A;
-    tr_vflux<LP>(s, w, k, L, fzm, fzp, lo, A);
+    tr_vflux<LP>(s, sf, w, k, L, fzm, fzp, lo, A);
     const double rp_b = lvl_dn<LP>(rp, k), rm_b = lvl_dn<LP>(rm, k);
     const double fcb = (k >= 1 && k <= L - 1) ? (A >= 0.0 ? fmin(rm_b, rp) : fmin(rp_b, rm)) * A : 0.0;
     const double fct = lvl_up<LP>(fcb, k);
@@ -540,8 +578,10 @@ __device__ __forceinline__ double tr_limited(double A, double m1, double p2, dou
 // SU (option "trsu"): su formed here as k_tr_bounds forms it -- the upwind sum over the
 // cell's edges (tr_bound_slot's order) and tr_bound_fin's expression -- instead of read
 // from X_su: the same values, one scratch array fewer (written once, read once)
-template <int LP, bool SELF, bool SU>
-__global__ __launch_bounds__(256) void k_tr_update(DevState S, double dt) {
+// RK (mpas_atm_advance_scalars_mono_rk): the interface high-order flux from the cell's scalars
+// column, read here before the new values are stored to it
+template <int LP, bool SELF, bool SU, bool RK>
+__device__ __forceinline__ void tr_update(const DevState& S, double dt) {
     int c, p;
     tr_slot<LP>(S, KC, c, p);
     const int L = S.L, k = (int)(threadIdx.x % LP);
@@ -556,6 +596,8 @@ __global__ __launch_bounds__(256) void k_tr_update(DevState S, double dt) {
     const double* so = fd(S, F_scalars_old);
     double sa, sb, sua = 0.0, sub = 0.0, rpa, rpb, rma, rmb;
     ld2<LP>(XP, so, c, p, k, sa, sb);
+    double sfa = sa, sfb = sb;
+    if constexpr (RK) ld2<LP>(XP, fd(S, F_scalars), c, p, k, sfa, sfb);
     if constexpr (!SU) ld2<LP>(XS, fd(S, X_su), c, p, k, sua, sub);
     ld2<LP>(XS, Rp, c, p, k, rpa, rpb);
     ld2<LP>(XS, Rm, c, p, k, rma, rmb);
@@ -602,8 +644,8 @@ __global__ __launch_bounds__(256) void k_tr_update(DevState S, double dt) {
             up(true, s1f, dv, u, y1b, y2b, hlb);
         }
         double loa, Aa_, lob, Ab_;
-        tr_vflux<LP>(sa, w, k, L, fzm, fzp, loa, Aa_);
-        tr_vflux<LP>(sb, w, k, L, fzm, fzp, lob, Ab_);
+        tr_vflux<LP>(sa, sa, w, k, L, fzm, fzp, loa, Aa_);
+        tr_vflux<LP>(sb, sb, w, k, L, fzm, fzp, lob, Ab_);
         const double lota = lvl_up<LP>(loa, k), lotb = lvl_up<LP>(lob, k);
         sua = (sa * r_o - dt * (hla * invA + (lota - loa) * rdzw)) / r_n;
         sub = (sb * r_o - dt * (hlb * invA + (lotb - lob) * rdzw)) / r_n;
@@ -646,9 +688,126 @@ __global__ __launch_bounds__(256) void k_tr_update(DevState S, double dt) {
         hca = hca + sg * tr_limited(Ba, n1a, q2a, q1a, n2a);
         hcb = hcb + sg * tr_limited(Bb, n1b, q2b, q1b, n2b);
     }
-    const double na = tr_update_fin<LP>(hca, sa, w, sua, rpa, rma, r_n, invA, rdzw, fzm, fzp, dt, k, L);
-    const double nb = tr_update_fin<LP>(hcb, sb, w, sub, rpb, rmb, r_n, invA, rdzw, fzm, fzp, dt, k, L);
+    const double na = tr_update_fin<LP>(hca, sa, sfa, w, sua, rpa, rma, r_n, invA, rdzw, fzm, fzp, dt, k, L);
+    const double nb = tr_update_fin<LP>(hcb, sb, sfb, w, sub, rpb, rmb, r_n, invA, rdzw, fzm, fzp, dt, k, L);
     if (k < L) st2<LP>(XP, fw(S, F_scalars), c, p, k, na, nb);  // level L keeps its value (the oracle writes 0..L-1)
+}
+template <int LP, bool SELF, bool SU>
+__global__ __launch_bounds__(256) void k_tr_update(DevState S, double dt) {
+    tr_update<LP, SELF, SU, false>(S, dt);
+}
+template <int LP, bool SELF>
+__global__ __launch_bounds__(256) void k_trk_update(DevState S, double dt) {
+    tr_update<LP, SELF, false, true>(S, dt);
+}
+
+// ---------------------------------------------------------------- unlimited stage
+// mpas_atm_advance_scalars: one stage of MPAS-A's atm_advance_scalars (the RK3 transport's
+// first two stages; include/mpas_dyn.h).  No upwind flux, no bounds, no R+ / R-: two launches,
+//   k_tra_edge   per edge: the high-order flux H of each scalar and level, k_tr_edge's sum
+//                over the adv list taken on scalars (X_Ah)
+//   k_tra_cell   per cell: the interface high-order flux V from the cell's own scalars
+//                column, the mass divergence D of ruAvg / wwAvg, rho_int = rho_old - dt D
+//                (MPAS's advance_density), scalars = (s_old rho_old - dt div(H, V)) / rho_int
+// The cell kernel reads its scalars column before it stores to it; no other wavefront reads
+// that column in the launch (H is the edge kernel's).
+template <int LP>
+__global__ __launch_bounds__(256) void k_tra_edge(DevState S) {
+    int e, p;
+    tr_slot<LP>(S, KE, e, p);
+    const int L = S.L, k = (int)(threadIdx.x % LP);
+    const Px XP = px_pub<LP>(L), XS = px_scr<LP>(S);
+    if (e >= S.nEO) return;
+    const int* rec = fi(S, X_eB) + (size_t)e * 24;  // advCellsForEdge(9) @12, nAdv @22
+    const int na = rec[22];
+    int adv[AF];
+    double ac[AF], ac3[AF];
+#pragma unroll
+    for (int j = 0; j < AF; j++) adv[j] = rec[12 + j];
+    row_ld(fd(S, F_adv_coefs) + (size_t)e * 15, ac);
+    row_ld(fd(S, F_adv_coefs_3rd) + (size_t)e * 15, ac3);
+    const double* sf = fd(S, F_scalars);
+    const double u = colk(fd(S, F_ruAvg), e);
+    double xa[AF], xb[AF];
+#pragma unroll
+    for (int j = 0; j < AF; j++) ld2<LP>(XP, sf, adv[j], p, k, xa[j], xb[j]);
+    const double sgn = copysign(1.0, u);
+    double acca = 0.0, accb = 0.0;
+#pragma unroll
+    for (int j = 0; j < AF; j++) {
+        const double wgt = ac[j] + sgn * ac3[j];
+        acca = add_if(j < na, acca, wgt * xa[j]);
+        accb = add_if(j < na, accb, wgt * xb[j]);
+    }
+    for (int j = AF; j < na; j++) {  // lists longer than the reference's 9 (width 15)
+        const int cj = fi(S, F_advCellsForEdge)[(size_t)e * 15 + j];
+        const double wgt = fd(S, F_adv_coefs)[(size_t)e * 15 + j] + sgn * fd(S, F_adv_coefs_3rd)[(size_t)e * 15 + j];
+        double ya, yb;
+        ld2<LP>(XP, sf, cj, p, k, ya, yb);
+        acca = acca + wgt * ya;
+        accb = accb + wgt * yb;
+    }
+    st2<LP>(XS, fw(S, X_Ah), e, p, k, PADW(u * acca), PADW(u * accb));
+}
+
+template <int LP>
+__global__ __launch_bounds__(256) void k_tra_cell(DevState S, double dt) {
+    int c, p;
+    tr_slot<LP>(S, KC, c, p);
+    const int L = S.L, k = (int)(threadIdx.x % LP);
+    const Px XP = px_pub<LP>(L), XS = px_scr<LP>(S);
+    if (c >= S.nCO) return;
+    const int ne = fi(S, F_nEdgesOnCell)[c];
+    const size_t r0 = (size_t)c * 10;
+    int e_[NF], s1_[NF];
+    double dv_[NF];
+    row_ld(fi(S, F_edgesOnCell) + r0, e_);
+    row_ld(fi(S, X_ce_s1) + r0, s1_);
+    row_ld(fd(S, X_ce_dv) + r0, dv_);
+    const double invA = fd(S, F_invAreaCell)[c];
+    const double rdzw = fd(S, F_rdzw)[k], fzm = fd(S, F_fzm)[k], fzp = fd(S, F_fzp)[k];
+    const double *ru = fd(S, F_ruAvg), *H = fd(S, X_Ah);
+    double soa, sob, sfa, sfb;
+    ld2<LP>(XP, fd(S, F_scalars_old), c, p, k, soa, sob);
+    ld2<LP>(XP, fd(S, F_scalars), c, p, k, sfa, sfb);
+    const double w = colk(fd(S, F_wwAvg), c), r_o = colk(fd(S, F_rho_zz_old_split), c);
+    double u_[NF], Ha[NF], Hb[NF];
+#pragma unroll
+    for (int i = 0; i < NF; i++) {
+        u_[i] = colk(ru, e_[i]);
+        ld2<LP>(XS, H, e_[i], p, k, Ha[i], Hb[i]);
+    }
+    double hd = 0.0, ha = 0.0, hb = 0.0;  // sums over the cell's edges: the mass flux, H of the two scalars
+#pragma unroll
+    for (int i = 0; i < NF; i++) {
+        const double sg = s1_[i] ? 1.0 : -1.0;
+        hd = add_if(i < ne, hd, sg * (dv_[i] * u_[i]));
+        ha = add_if(i < ne, ha, sg * Ha[i]);
+        hb = add_if(i < ne, hb, sg * Hb[i]);
+    }
+    for (int i = NF; i < ne; i++) {  // cells with more than NF edges
+        const size_t r = r0 + i;
+        const int e = fi(S, F_edgesOnCell)[r];
+        const double sg = fi(S, X_ce_s1)[r] ? 1.0 : -1.0;
+        const double dv = fd(S, X_ce_dv)[r], u = colk(ru, e);
+        double Ba, Bb;
+        ld2<LP>(XS, H, e, p, k, Ba, Bb);
+        hd = hd + sg * (dv * u);
+        ha = ha + sg * Ba;
+        hb = hb + sg * Bb;
+    }
+    // interface k (the lane's lower one) and k + 1; no flux through interfaces 0 and L,
+    // whose wwAvg is not used
+    const bool in = k >= 1 && k <= L - 1;
+    const double wb = in ? w : 0.0, wt = lvl_up<LP>(wb, k);
+    const double via = tr_vhi<LP>(sfa, w, k, L, fzm, fzp), vib = tr_vhi<LP>(sfb, w, k, L, fzm, fzp);
+    const double vba = in ? via : 0.0, vbb = in ? vib : 0.0;
+    const double vta = lvl_up<LP>(vba, k), vtb = lvl_up<LP>(vbb, k);
+    const double D = invA * hd + rdzw * (wt - wb);
+    const double r_i = r_o - dt * D;
+    const double na = (soa * r_o - dt * (invA * ha + rdzw * (vta - vba))) / r_i;
+    const double nb = (sob * r_o - dt * (invA * hb + rdzw * (vtb - vbb))) / r_i;
+    if (k < L) st2<LP>(XP, fw(S, F_scalars), c, p, k, na, nb);  // level L keeps its value
 }
 
 // ---------------------------------------------------------------- tiled transport
@@ -796,7 +955,7 @@ __global__ __launch_bounds__(TRT_THREADS, TRT_WAVES) void k_trt_bounds(DevState 
             tr_bound_slot(true, t.s1(i), t.dv(i), u, x1, x2, A, r);
         }
         double Rp, Rm, su;
-        tr_bound_fin<LP>(r, s, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rp, Rm, su);
+        tr_bound_fin<LP>(r, s, s, w, r_o, r_n, invA, rdzw, fzm, fzp, dt, k, L, Rp, Rm, su);
         if (k < L) {  // (the scratch holds levels 0..L-1 only: px_scr)
             sat<LP>(XS, fw(S, X_Rp), c, sc, k) = Rp;
             sat<LP>(XS, fw(S, X_Rm), c, sc, k) = Rm;
@@ -861,10 +1020,10 @@ __global__ __launch_bounds__(TRT_THREADS, TRT_WAVES) void k_trt_update(DevState 
             hc = hc + sg * tr_limited(A, m1, p2, p1, m2);
         }
         double lob, Ab;
-        tr_vflux<LP>(s, w, k, L, fzm, fzp, lob, Ab);
+        tr_vflux<LP>(s, s, w, k, L, fzm, fzp, lob, Ab);
         const double lot = lvl_up<LP>(lob, k);
         const double su = (s * r_o - dt * (hlo * invA + (lot - lob) * rdzw)) / r_n;
-        const double sn = tr_update_fin<LP>(hc, s, w, su, rp, rm, r_n, invA, rdzw, fzm, fzp, dt, k, L);
+        const double sn = tr_update_fin<LP>(hc, s, s, w, su, rp, rm, r_n, invA, rdzw, fzm, fzp, dt, k, L);
         if (k < L) sat<LP>(XP, fw(S, F_scalars), c, sc, k) = sn;
     }
 }
@@ -973,6 +1132,71 @@ hipError_t launch_advance_scalars_mono(const DevState& S, hipStream_t st, double
     if (fold && (S.halo || S.trt || S.tre || S.trsu)) return hipErrorInvalidValue;
     if (S.trt) MPAS_LP_DISPATCH(S.LP, transport_tiled, S, st, dt);
     MPAS_LP_DISPATCH(S.LP, transport_lp, S, st, dt, fold);
+}
+
+// column-slot blocks of a launch over the owned entities [lo, end) of a kind
+template <int LP>
+static int tr_blocks(const DevState& X, int kind) {
+    constexpr int COLS = 256 / LP;
+    const int end = kind == KC ? X.nCO : X.nEO;
+    const long n = (long)(end - X.lo[kind]) * (NSC / 2);
+    return n > 0 ? (int)((n + COLS - 1) / COLS) : 0;
+}
+
+// one unlimited stage: scalars (the previous stage's estimate) is gathered over the adv lists
+template <int LP>
+static hipError_t advance_scalars_lp(const DevState& S, hipStream_t st, double dt) {
+    auto ke = [&](const DevState& X) {
+        const int nb = tr_blocks<LP>(X, KE);
+        if (nb) k_tra_edge<LP><<<nb, 256, 0, st>>>(X);
+    };
+    HALO_RUN(S, st, ke, F_scalars, F_ruAvg);
+    HALO_WROTE(S, X_Ah);
+    auto kc = [&](const DevState& X) {
+        const int nb = tr_blocks<LP>(X, KC);
+        if (nb) k_tra_cell<LP><<<nb, 256, 0, st>>>(X, dt);
+    };
+    HALO_RUN(S, st, kc, F_ruAvg, X_Ah);
+    HALO_WROTE(S, F_scalars);
+    return hipGetLastError();
+}
+hipError_t launch_advance_scalars(const DevState& S, hipStream_t st, double dt) {
+    MPAS_LP_DISPATCH(S.LP, advance_scalars_lp, S, st, dt);
+}
+
+// the monotonic task with its two high-order fluxes taken on scalars: transport_lp's three
+// launches in their RK forms (the default kernels only: the caller refuses the variants)
+template <int LP>
+static hipError_t transport_rk_lp(const DevState& S0, hipStream_t st, double dt) {
+    DevState S = S0;
+    S.trsave = 0;
+    auto ke = [&](const DevState& X) {
+        const int nb = tr_blocks<LP>(X, KE);
+        if (nb) k_trk_edge<LP><<<nb, 256, 0, st>>>(X);
+    };
+    HALO_RUN(S, st, ke, F_scalars, F_scalars_old, F_ruAvg);
+    HALO_WROTE(S, X_Ah);
+    auto kb = [&](const DevState& X) {
+        const int nb = tr_blocks<LP>(X, KC);
+        if (!nb) return;
+        if (X.selfc) k_trk_bounds<LP, true><<<nb, 256, 0, st>>>(X, dt);
+        else k_trk_bounds<LP, false><<<nb, 256, 0, st>>>(X, dt);
+    };
+    HALO_RUN(S, st, kb, F_scalars_old, F_ruAvg, X_Ah);
+    HALO_WROTE(S, X_Rp, X_Rm, X_su);
+    auto ku = [&](const DevState& X) {
+        const int nb = tr_blocks<LP>(X, KC);
+        if (!nb) return;
+        if (X.selfc) k_trk_update<LP, true><<<nb, 256, 0, st>>>(X, dt);
+        else k_trk_update<LP, false><<<nb, 256, 0, st>>>(X, dt);
+    };
+    HALO_RUN(S, st, ku, X_Ah, X_Rp, X_Rm);
+    HALO_WROTE(S, F_scalars);
+    return hipGetLastError();
+}
+hipError_t launch_advance_scalars_mono_rk(const DevState& S, hipStream_t st, double dt) {
+    if (S.trt || S.tre || S.trsu || S.trepw == 2) return hipErrorInvalidValue;
+    MPAS_LP_DISPATCH(S.LP, transport_rk_lp, S, st, dt);
 }
 
 }  // namespace mpas

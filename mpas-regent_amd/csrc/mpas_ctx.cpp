@@ -88,7 +88,9 @@ struct mpas_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     int exact = 0;
-    int transport = 0;  // option "transport": atm_srk3 runs the monotonic scalar transport (physics = 1)
+    // option "transport": atm_srk3 runs the scalar transport (physics >= 1) -- 1 the monotonic task once
+    // over dt, 2 MPAS's RK3 form: two unlimited stages over dt/3 and dt/2, then the monotonic task over dt
+    int transport = 0;
     int self_on = 1;   // option "self": allow the SELF gathers when the mesh permits
     int self_ok = 0;   // k_prepare's verdict on the uploaded mesh
     int overlap = 1;   // option "overlap": halo exchanges beside interior compute
@@ -898,6 +900,12 @@ const char* recover_name(int rk_step) {
     return rk_step == 2 ? "atm_recover_large_step_variables_work[rk2]" : "atm_recover_large_step_variables_work[rk<2]";
 }
 
+// the RK3 transport's tasks have the default transport kernels only
+void tr_rk_supported(mpas_ctx* c, const char* what) {
+    if (c->trtile || c->tredge || c->S.trsu || c->S.trepw == 2)
+        throw Fail{MPAS_ENOTSUP, std::string(what) + ": not with trtile, tredge, trsu or trepw = 2"};
+}
+
 void srk3(mpas_ctx* c, double dt, int schedule) {
     // rk_timestep.rg:378-399
     const int number_of_sub_steps = 2;
@@ -913,7 +921,8 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
     hipStream_t st = c->stream;
     // option trsave: the copy below folded into the transport's bounds kernel (its tables decided here:
     // the tiled and LDS-edge forms need none of them built, su stored)
-    const bool trfold = c->transport && c->trsave && !c->halo && !c->trtile && !c->tredge && !S.trsu;
+    // (transport = 2: the separate copy -- its first stage reads scalars and scalars_old)
+    const bool trfold = c->transport == 1 && c->trsave && !c->halo && !c->trtile && !c->tredge && !S.trsu;
     if (c->transport && !trfold) {
         // the time level the transport starts from (MPAS-A scalars(time level 1)); the
         // copy carries the ghosts of scalars, fresh or not, so scalars_old is as stale
@@ -1166,7 +1175,16 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                      [&] { return launch_solve_diagnostics(S, st, 0, rk_step, live ? 7 : 3, nv); });
         }
     }
-    if (c->transport)  // after the last stage's recover: ruAvg / wwAvg / rho_zz of the step
+    if (c->transport == 2) {
+        // MPAS's RK3 transport (dynamics and transport split): every stage from scalars_old with the
+        // step's ruAvg / wwAvg / rho_zz_old_split, its high-order fluxes from the stage before
+        run_task(c, "atm_advance_scalars", [&] { return launch_advance_scalars(S, st, dt / 3); });
+        run_task(c, "atm_advance_scalars", [&] { return launch_advance_scalars(S, st, dt / 2); });
+        run_task(c, "atm_advance_scalars_mono_rk", [&] {
+            trt_ensure(c);
+            return launch_advance_scalars_mono_rk(S, st, dt);
+        });
+    } else if (c->transport)  // after the last stage's recover: ruAvg / wwAvg / rho_zz of the step
         run_task(c, trfold ? "atm_advance_scalars_mono[save]" : "atm_advance_scalars_mono", [&] {
             trt_ensure(c);  // (built before a capture by prepare_now)
             return launch_advance_scalars_mono(S, st, dt, trfold ? 1 : 0);
@@ -1542,8 +1560,9 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
             c->ett_clo = (int)value;
             c->ett_dirty = true;
         } else if (name && std::strcmp(name, "transport") == 0) {
+            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "transport must be 0, 1 (one monotonic update) or 2 (RK3)"};
             if (value && !c->S.physics) throw Fail{MPAS_EINVAL, "transport needs physics = 1 (it reads the recovered ruAvg, wwAvg, rho_zz)"};
-            c->transport = value ? 1 : 0;
+            c->transport = (int)value;
         } else if (name && std::strcmp(name, "overlap") == 0) {
             c->overlap = value ? 1 : 0;
             if (c->halo) c->halo->overlap = c->overlap;
@@ -2135,6 +2154,23 @@ int mpas_atm_advance_scalars_mono(mpas_ctx* c, double dt) {
         });
     });
 }
+int mpas_atm_advance_scalars(mpas_ctx* c, double dt) {
+    if (!c) return MPAS_EINVAL;
+    return guarded(c, [&] {
+        tr_rk_supported(c, "atm_advance_scalars");
+        run_task(c, "atm_advance_scalars", [&] { return launch_advance_scalars(c->S, c->stream, dt); });
+    });
+}
+int mpas_atm_advance_scalars_mono_rk(mpas_ctx* c, double dt) {
+    if (!c) return MPAS_EINVAL;
+    return guarded(c, [&] {
+        tr_rk_supported(c, "atm_advance_scalars_mono_rk");
+        run_task(c, "atm_advance_scalars_mono_rk", [&] {
+            trt_ensure(c);
+            return launch_advance_scalars_mono_rk(c->S, c->stream, dt);
+        });
+    });
+}
 int mpas_atm_compute_output_diagnostics(mpas_ctx* c) {
     MPAS_TASK("atm_compute_output_diagnostics", launch_output_diagnostics(c->S, c->stream));
 }
@@ -2162,6 +2198,7 @@ int mpas_summarize_timestep(mpas_ctx* c, int detailed, int global_vel, int globa
 int mpas_atm_srk3(mpas_ctx* c, double dt, int schedule) {
     return guarded(c, [&] {
         hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        if (c->transport == 2) tr_rk_supported(c, "atm_srk3 with transport = 2");  // (never inside a capture)
         srk3_step(c, dt, schedule);
     });
 }

@@ -304,6 +304,11 @@ hipError_t launch_output_diagnostics(const DevState& S, hipStream_t st);
 // fold (atm_srk3, option "trsave"): scalars_save not run before -- scalars still holds the old values,
 // and the bounds kernel stores them to scalars_old (undecomposed, default kernels only)
 hipError_t launch_advance_scalars_mono(const DevState& S, hipStream_t st, double dt, int fold = 0);
+// the RK3 transport's stages (k_transport.hip): one unlimited stage from scalars_old with the
+// fluxes of scalars, and the monotonic task with its high-order fluxes taken on scalars
+// (the default transport kernels only)
+hipError_t launch_advance_scalars(const DevState& S, hipStream_t st, double dt);
+hipError_t launch_advance_scalars_mono_rk(const DevState& S, hipStream_t st, double dt);
 hipError_t launch_damping_coefs(const DevState& S, hipStream_t st, double zd, double xnutr);
 hipError_t launch_compute_signs(const DevState& S, hipStream_t st);
 // strided device view <-> LP-padded 3-D field (elem 8: fp64, 1: uint8 masks)

@@ -4,7 +4,7 @@ state -> atm_core_init's one-time precompute -> time steps -> atm_compute_output
 
     python -m mpasdyn.driver [--grid x1.N.grid.nc] [--levels 26] [--steps 10] [--dt 720]
                              [--schedule 1] [--physics {0,1,2}] [--transport] [--day]
-                             [--out timestep_output.nc]
+                             [--transport-scheme {single,rk3}] [--out timestep_output.nc]
 
 Without --grid the reference's own x1.2562 mesh (tests/golden fixture) is used.  The mesh
 is taken in mpas-mode (0-based) ids, the ids the JW state (mpasdyn/jw.py) is defined on.
@@ -15,7 +15,9 @@ per step with the reference's global min/max of w and u (summarize_timestep).
 the JW state then evolves as a dynamical core; the run starts from MPAS-A's initial
 diagnostics (solve_diagnostics at rk_step -1 and the cell-centre winds, atm_core.rg:30-33)
 and reports the surface pressure (min/max/mean, hPa) and the global dry mass after the
-last step; `--day` sets the steps to one simulated day (86400 / dt)."""
+last step; `--day` sets the steps to one simulated day (86400 / dt).  `--transport` advects the
+8 scalars: `--transport-scheme single` (default) with one monotonic update over dt, `rk3` with
+MPAS-A's three-stage RK3 (option "transport" = 2, include/mpas_dyn.h)."""
 import argparse
 import os
 import sys
@@ -25,6 +27,7 @@ import numpy as np
 
 def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=False, out=None, device=0,
         log=print):
+    """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport"""
     from . import build_state as bs
     from . import jw, lib
     from . import mesh as M
@@ -74,6 +77,8 @@ def main(argv=None):
     ap.add_argument("--physics", type=int, default=0, choices=[0, 1, 2])
     ap.add_argument("--day", action="store_true", help="one simulated day: steps = 86400 / dt")
     ap.add_argument("--transport", action="store_true")
+    ap.add_argument("--transport-scheme", choices=["single", "rk3"], default="single",
+                    help="with --transport: one monotonic update over dt, or MPAS-A's RK3 (two unlimited stages first)")
     ap.add_argument("--out", default="timestep_output.nc")
     a = ap.parse_args(argv)
     from . import mesh as M
@@ -83,7 +88,8 @@ def main(argv=None):
     else:
         m = M.load_x1_2562()
     steps = int(round(86400.0 / a.dt)) if a.day else a.steps
-    run(m, a.levels, steps, a.dt, a.schedule, a.physics, a.transport, a.dt_from_step, a.out)
+    transport = (2 if a.transport_scheme == "rk3" else 1) if a.transport else 0
+    run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out)
     return 0
 
 

@@ -31,6 +31,8 @@ KERNEL_TASK = [
     (r"k_solve_", "atm_compute_solve_diagnostics"),
     (r"k_finish_|k_finish64", "atm_rk_dynamics_substep_finish"),
     (r"k_recover_", "atm_recover_large_step_variables_work"),
+    (r"k_tra_", "atm_advance_scalars"),
+    (r"k_trk_", "atm_advance_scalars_mono_rk"),
     (r"k_tr_", "atm_advance_scalars_mono"),
 ]
 FETCH_FACTOR = 2.0  # MI355X_MICROARCH.md: gfx950 FETCH_SIZE is half the fetched bytes

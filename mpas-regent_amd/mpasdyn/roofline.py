@@ -243,6 +243,13 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
         return (["scalars" if save else "scalars_old", "ruAvg", "wwAvg", "rho_zz_old_split", "rho_zz", "cellsOnEdge",
                  "advCellsForEdge", "nAdvCellsForEdge", "adv_coefs", "adv_coefs_3rd", "dvEdge", "edgesOnCell",
                  "nEdgesOnCell", "invAreaCell"], ["scalars"] + (["scalars_old"] if save else []))
+    if task == "atm_advance_scalars":  # one unlimited stage of the RK3 transport (k_tra_*): no rho_zz
+        return (["scalars_old", "scalars", "ruAvg", "wwAvg", "rho_zz_old_split", "cellsOnEdge", "advCellsForEdge", "nAdvCellsForEdge",
+                 "adv_coefs", "adv_coefs_3rd", "dvEdge", "edgesOnCell", "nEdgesOnCell", "invAreaCell"], ["scalars"])
+    if task == "atm_advance_scalars_mono_rk":  # the monotonic task with its high-order fluxes from scalars (k_trk_*)
+        return (["scalars_old", "scalars", "ruAvg", "wwAvg", "rho_zz_old_split", "rho_zz", "cellsOnEdge",
+                 "advCellsForEdge", "nAdvCellsForEdge", "adv_coefs", "adv_coefs_3rd", "dvEdge", "edgesOnCell",
+                 "nEdgesOnCell", "invAreaCell"], ["scalars"])
     if task == "scalars_save":  # srk3 with transport: scalars_old = scalars
         return ["scalars"], ["scalars_old"]
     if task == "mpas_reconstruct_2d":
@@ -288,7 +295,8 @@ def step_schedule(schedule=1, physics=0, transport=0, fusedamp=False, fusesetup=
                   msml=False):
     """(task, kwargs, launches) of one atm_srk3 step (rk_timestep.rg:404-481); physics = 1
     (the MPAS vertical solver): number_sub_steps acoustic substeps (4 per step) and
-    recover after each stage; transport = 1 adds the scalar save and the transport;
+    recover after each stage; transport = 1 adds the scalar save and the transport, transport = 2
+    the save, two unlimited stages and the monotonic task's RK form;
     fusedamp (reference semantics): six of the seven dampings run inside the next acoustic
     launch; fusecopy (with fusesetup): setup's edge copies in stage 0's dyn_tend"""
     copy = bool(fusesetup and fusecopy)
@@ -323,7 +331,9 @@ def step_schedule(schedule=1, physics=0, transport=0, fusedamp=False, fusesetup=
                 ("atm_rk_dynamics_substep_finish", p, 1)]
         if physics == 2:
             out.append(("mpas_reconstruct_2d", {}, 1))
-        if transport and trsave:  # (option trsave: scalars_save folded into the transport)
+        if transport == 2:  # (the RK3 transport: always the separate copy)
+            out += [("scalars_save", {}, 1), ("atm_advance_scalars", {}, 2), ("atm_advance_scalars_mono_rk", {}, 1)]
+        elif transport and trsave:  # (option trsave: scalars_save folded into the transport)
             out += [("atm_advance_scalars_mono", {"save": True}, 1)]
         elif transport:
             out += [("scalars_save", {}, 1), ("atm_advance_scalars_mono", {}, 1)]

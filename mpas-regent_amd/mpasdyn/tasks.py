@@ -138,6 +138,19 @@ def atm_advance_scalars_mono(ctx, dt):
     ctx._check(ctx.lib.mpas_atm_advance_scalars_mono(ctx.h, float(dt)), "atm_advance_scalars_mono")
 
 
+def atm_advance_scalars(ctx, dt):
+    """One unlimited stage of MPAS-A's atm_advance_scalars: scalars_old advanced over dt with the
+    high-order fluxes of scalars, into scalars (the RK3 transport's first two stages;
+    include/mpas_dyn.h)"""
+    ctx._check(ctx.lib.mpas_atm_advance_scalars(ctx.h, float(dt)), "atm_advance_scalars")
+
+
+def atm_advance_scalars_mono_rk(ctx, dt):
+    """atm_advance_scalars_mono with its high-order fluxes taken on scalars, the previous stage's
+    estimate (the RK3 transport's last stage; include/mpas_dyn.h)"""
+    ctx._check(ctx.lib.mpas_atm_advance_scalars_mono_rk(ctx.h, float(dt)), "atm_advance_scalars_mono_rk")
+
+
 def summarize_timestep(ctx, config_print_detailed_minmax_vel=False, config_print_global_minmax_vel=False,
                        config_print_global_minmax_sca=False):
     """rk_timestep.rg:29; returns the 31 values the reference prints (layout: include/mpas_dyn.h)"""

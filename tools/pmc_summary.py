@@ -41,6 +41,9 @@ LAUNCHES = {"atm_rk_integration_setup": 1, "atm_compute_moist_coefficients": 1, 
 LAUNCHES_PHYSICS = dict(LAUNCHES, atm_advance_acoustic_step_work=4, atm_divergence_damping_3d=4,
                         atm_set_smlstep_pert_variables_work=3, atm_recover_large_step_variables_work=3,
                         atm_advance_scalars_mono=1)
+# (option transport = 2: the RK3 transport in place of the single monotonic update)
+LAUNCHES_RK3 = dict({k: v for k, v in LAUNCHES_PHYSICS.items() if k != "atm_advance_scalars_mono"},
+                    atm_advance_scalars=2, atm_advance_scalars_mono_rk=1)
 
 
 def read_counter(d, counter):
@@ -67,9 +70,12 @@ def main():
     ap.add_argument("--dims", nargs=4, type=int, required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--physics", action="store_true", help="the run was bench.py --physics or --transport")
+    ap.add_argument("--rk3", action="store_true", help="the run had option transport = 2 (implies --physics)")
     a = ap.parse_args()
     global LAUNCHES
-    if a.physics:
+    if a.rk3:
+        LAUNCHES = LAUNCHES_RK3
+    elif a.physics:
         LAUNCHES = LAUNCHES_PHYSICS
     nC, nE, nV, L = a.dims
     out = {"dims": a.dims, "kernels": {}, "tasks": {}}
