@@ -56,6 +56,7 @@ struct DynK {
     double rud;  // (option mru, the MPAS dynamics, fast path) the stage's dts: the kernel forming the final
                  // tend_u also stores the first substep's ru_p = dts tend_u and ruAvg = ru_p
     int nhd;     // (option ntu, rk_step 0 with B forming no tend_u) A's h_divergence is dead: not stored
+    int cpA;     // (cp, where B would load u and ru for the copies alone) A makes them: dyn_A_body CPA
 };
 
 // option mru (the MPAS dynamics, atm_srk3 fast path): the stage's first acoustic substep begins with
@@ -76,8 +77,15 @@ __device__ __forceinline__ void ru_first(const DevState& S, double dts, int e, i
 // SETUP (atm_srk3 stage 0 beside the fused setup launch, option hfuse): rho_p_save and qtot
 // are being written by that launch -- rho_p_save = rho_p and qtot = 0 at every level A
 // stores (k != L) -- so A takes rho_p and 0.0 instead: the same values
-template <int LP, bool RK0, bool MD, bool SETUP = false>
+// CPA (a.cpA: atm_srk3 stage 0, option "fusecopy", where B forms neither tend_u nor the theta flux and
+// would load u and ru for the copies alone): setup's edge copies ru_save = ru, u_2 = u (:758-761, every
+// level but L) made here, from the ru and u this kernel gathers at the cell's edges for h_divergence and
+// the Smagorinsky kdiff -- each edge by the one (cell, slot) that owns it (X_eown, the fused damping's
+// ownership), the edges no cell lists by k_dyn_cp_orph -- and B loads neither column.  The bytes are
+// B's put2: the raw value below level L, 0.0 in the padding, level L untouched
+template <int LP, bool RK0, bool MD, bool SETUP = false, bool CPA = false>
 __device__ __forceinline__ void dyn_A_body(const DevState& S, const DynK& a, Blk bk) {
+    static_assert(!CPA || (RK0 && !MD && !SETUP), "the edge copies in A: rk_step 0, reference semantics, its own launch");
     ColMap<LP> m(S, KC, bk);
     const int L = S.L, k = m.k, c = m.ent;
     if (c >= S.nCO) return;
@@ -101,11 +109,14 @@ __device__ __forceinline__ void dyn_A_body(const DevState& S, const DynK& a, Blk
     const int ne = cell_rec<false>(S, c, e_, c1_, c2_);
     row_ld(eocs, eocs_);
     row_ld(cdv, cdv_);
+    const int own = CPA ? fi(S, X_eown)[c] : 0;
 #pragma unroll
     for (int i = 0; i < NF; i += 2) gather2s<LP>(ru, e_[i], e_[i + 1], k, ru_[i], ru_[i + 1]);
+    // (the masks keep the raw value below level L and give 0.0 above it: the copies' bytes at every
+    // level they store, CPA)
 #pragma unroll
     for (int i = 0; i < NF; i++) ru_[i] = ldz(live, ru_[i]);
-    if (smag) {
+    if (smag || CPA) {  // (CPA: the copies need u whatever the mixing)
 #pragma unroll
         for (int i = 0; i < NF; i += 2) {
             gather2s<LP>(u, e_[i], e_[i + 1], k, u_[i], u_[i + 1]);
@@ -160,6 +171,17 @@ __device__ __forceinline__ void dyn_A_body(const DevState& S, const DynK& a, Blk
             kd = dmax_(kd, (pw == 0 ? 1.0 : 2.0) * 2.0833 * kLenDisp * a.cam_coef);
         }
         colk(fw(S, F_kdiff), c) = KEEPW(kd, kl_kd);
+    }
+    // CPA: the copies of the edges this cell owns, after the column's last load
+    if constexpr (CPA) {
+        double *rus_o = fw(S, F_ru_save), *u2_o = fw(S, F_u_2);
+#pragma unroll
+        for (int i = 0; i < NF; i++) {
+            if (((own >> i) & 1) && k != L) {
+                colk(rus_o, e_[i]) = ru_[i];
+                colk(u2_o, e_[i]) = u_[i];
+            }
+        }
     }
 
     // ---- h_divergence (:924-938)
@@ -221,10 +243,32 @@ __device__ __forceinline__ void dyn_A_body(const DevState& S, const DynK& a, Blk
     }
     if (a.nhd) colk(fw(S, X_wc), c) = k < L ? wc : 0.0;  // (option ntu: h_divergence read by no kernel)
     else put2f<LP>(fw(S, F_h_divergence), c, fw(S, X_wc), c, k, KEEPW(hd, kl_hd), k < L ? wc : 0.0);
+    if constexpr (CPA) {  // (the generic tail: an edge owned through a slot past NF)
+        for (int i = NF; i < ne; i++) {
+            if (((own >> i) & 1) && k != L) {
+                const int e = eoc[i];
+                colk(fw(S, F_ru_save), e) = PADW(colk(ru, e));
+                colk(fw(S, F_u_2), e) = PADW(colk(u, e));
+            }
+        }
+    }
 }
-template <int LP, bool RK0, bool MD>
+template <int LP, bool RK0, bool MD, bool CPA = false>
 __global__ __launch_bounds__(256) void k_dyn_A(DevState S, DynK a) {
-    dyn_A_body<LP, RK0, MD>(S, a, this_blk());
+    dyn_A_body<LP, RK0, MD, false, CPA>(S, a, this_blk());
+}
+// CPA: the edges no cell lists (X_orph), copied by blocks of their own (as k_acoustic_orph)
+template <int LP>
+__global__ __launch_bounds__(256) void k_dyn_cp_orph(DevState S) {
+    const int L = S.L, k = (int)(threadIdx.x % LP);
+    const int j = col_of<LP>((int)blockIdx.x);
+    if (j >= S.n_orph) return;
+    const int e = fi(S, X_orph)[j];
+    const double ru = colk(fd(S, F_ru), e), u = colk(fd(S, F_u), e);
+    if (k != L) {
+        colk(fw(S, F_ru_save), e) = PADW(ru);
+        colk(fw(S, F_u_2), e) = PADW(u);
+    }
 }
 
 // ------------------------------------------------------------------------ B (edges)
@@ -248,9 +292,12 @@ __global__ __launch_bounds__(256) void k_dyn_A(DevState S, DynK a) {
 // h_divergence at the cells, tend_ru_physics).  The kernel keeps what later kernels read:
 // tend_u_euler (the pressure gradient and del2, :964-970, :1030-1048), delsq_u, the theta flux,
 // setup's copies
-template <int LP, bool RK0, bool MD, bool HF, bool DIN = false, bool NOF = false, bool NTU = false>
+// NCP (a.cpA: rk_step 0, NOF and NTU): A has made setup's copies (dyn_A_body CPA); nothing else here reads u or
+// ru at the edge, so neither column is loaded
+template <int LP, bool RK0, bool MD, bool HF, bool DIN = false, bool NOF = false, bool NTU = false, bool NCP = false>
 __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState S, DynK a) {
     static_assert(!NTU || !MD, "the dead tend_u: reference semantics");
+    static_assert(!NCP || (RK0 && NOF && NTU), "u and ru dead at the edge: no tend_u, no flux, no rk > 0 perturbation flux");
     ColMap<LP> m(S, KE);
     const int L = S.L, k = m.k, e = m.ent;
     if (e >= S.nEO) return;
@@ -269,7 +316,7 @@ __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState
     // instruction; the raw halves, swapped after the scheduling barrier below)
     double u, ru_e, rw1, rw2, w1, w2, rho_edge, pv;
     const double2 z2 = make_double2(0.0, 0.0);
-    const double2 g_uru = gather2_ld<LP>(u_f, e, fd(S, F_ru), e, k);
+    const double2 g_uru = NCP ? z2 : gather2_ld<LP>(u_f, e, fd(S, F_ru), e, k);
     const double2 g_rw = NTU ? z2 : gather2s_ld<LP>(fd(S, F_rw), cell1, cell2, k);
     const double2 g_w = NTU ? z2 : gather2s_ld<LP>(fd(S, F_w), cell1, cell2, k);
     const double2 g_rp = NTU ? make_double2(colk(fd(S, F_rho_edge), e), 0.0) : gather2_ld<LP>(fd(S, F_rho_edge), e, pv_f, e, k);
@@ -366,7 +413,8 @@ __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState
     // coefficients after it: cache hits, no registers held across the batch)
     __builtin_amdgcn_sched_barrier(0);
     const double fzm = fd(S, F_fzm)[k], fzp = fd(S, F_fzp)[k], rdzw = fd(S, F_rdzw)[k];
-    g2_fin<LP>(g_uru, u, ru_e);
+    if constexpr (NCP) u = ru_e = 0.0;
+    else g2_fin<LP>(g_uru, u, ru_e);
     if constexpr (NTU) {  // (not loaded as pairs: no swaps)
         rw1 = rw2 = w1 = w2 = pv = 0.0;
         rho_edge = g_rp.x;
@@ -572,7 +620,7 @@ __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState
     // (:758-761, every level but L) from the u and ru columns this kernel has loaded; no
     // task between setup and here reads ru_save or u_2 (dyn_tend reads ru_save at
     // rk_step > 0 only, after this kernel), and u / ru are not written in between
-    if (a.cp) put2<LP>(fw(S, F_ru_save), e, fw(S, F_u_2), e, k, PADW(ru_e), PADW(u), k != L, k != L);
+    if (!NCP && a.cp) put2<LP>(fw(S, F_ru_save), e, fw(S, F_u_2), e, k, PADW(ru_e), PADW(u), k != L, k != L);
     if constexpr (HF) {  // every lane stores (paired 16-B stores); level L keeps its value
         double* Fo = fw(S, X_F);
         double* tuo = fw(S, F_tend_u);
@@ -1017,7 +1065,9 @@ __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int
     double urz = 0.0, urm = 0.0, Fw_[NF], ru_l = 0.0, wfl[2];
     if constexpr (WCE) {
         col_rd2<LP>(fd(S, F_uReconstructZonal), fd(S, F_uReconstructMeridional), c, k, L, urz, urm);
-        rw = colk(fd(S, F_rw), c);
+        // (NTH: rho_zz rides with rw -- its usual partner tend_theta_euler is dead there, below)
+        if constexpr (NTH) gather2<LP>(fd(S, F_rw), c, fd(S, F_rho_zz), c, k, rw, rho_zz);
+        else rw = colk(fd(S, F_rw), c);
         int el = 0;  // the cell's last edge (Q13: ru_edge_w of the last edge)
 #pragma unroll
         for (int i = 0; i < NF; i++) el = (i == ne - 1) ? e_[i] : el;
@@ -1037,8 +1087,21 @@ __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int
     else pp = dpdz = 0.0;
     if constexpr (NTH) rws = tms = 0.0;  // (wdtz's, dead)
     else gather2<LP>(fd(S, F_rw_save), c, tms_f, c, k, rws, tms);
-    gather2<LP>(tm, c, fd(S, F_tend_w_euler), c, k, tmv, twe);
-    gather2<LP>(fd(S, F_tend_theta_euler), c, fd(S, F_rho_zz), c, k, tte, rho_zz);
+    if constexpr (NTH) {
+        // theta_m feeds only the dead wdtz; tend_theta_euler is live at rk_step 0 alone (its del4 and store),
+        // rho_zz at rk_step > 0 alone (the w scratch, loaded with rw above): the live columns, paired
+        tmv = 0.0;
+        if constexpr (RK0) {
+            gather2<LP>(fd(S, F_tend_w_euler), c, fd(S, F_tend_theta_euler), c, k, twe, tte);
+            rho_zz = 0.0;
+        } else {
+            twe = colk(fd(S, F_tend_w_euler), c);
+            tte = 0.0;
+        }
+    } else {
+        gather2<LP>(tm, c, fd(S, F_tend_w_euler), c, k, tmv, twe);
+        gather2<LP>(fd(S, F_tend_theta_euler), c, fd(S, F_rho_zz), c, k, tte, rho_zz);
+    }
     if constexpr (NTH) rt_diab = trp = 0.0;
     else gather2<LP>(fd(S, F_rt_diabatic_tend), c, fd(S, F_tend_rtheta_physics), c, k, rt_diab, trp);
     if (rk0) {
@@ -1507,12 +1570,13 @@ static DynK make_dynk(const DevState& S, const DynTendArgs& in) {
     // (option ntu at rk_step 0 where B forms no tend_u -- dyn_lp_md's `ntu`: h_divergence, which only tend_u
     // reads, is dead; the last stage's A rewrites it)
     a.nhd = (S.physics == 0 && in.ntu && in.rk_step == 0 && !(a.h4 > 0.0 && !a.d4o)) ? 1 : 0;
+    a.cpA = 0;  // (dyn_lp_md, which knows the edge kernel's form)
     return a;
 }
 
 template <int LP, bool MD>
 static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs& in) {
-    const DynK a = make_dynk(S, in);
+    DynK a = make_dynk(S, in);
     const bool rk0 = a.rk_step == 0, del4 = rk0 && a.h4 > 0.0;
     // HF: the fast path's theta flux per edge formed in B (E sums eocs H; reassociated, so
     // exact mode keeps the reference's per-cell order)
@@ -1522,6 +1586,14 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     auto kA = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KC);
         if (!nb) return;
+        if constexpr (!MD) {
+            if (a.cpA) {  // (with setup's edge copies; the edges no cell lists in a launch of their own)
+                k_dyn_A<LP, true, false, true><<<nb, 256, 0, st>>>(X, a);
+                const int nob = (X.n_orph + 256 / LP - 1) / (256 / LP);
+                if (nob) k_dyn_cp_orph<LP><<<nob, 256, 0, st>>>(X);
+                return;
+            }
+        }
         if (rk0) k_dyn_A<LP, true, MD><<<nb, 256, 0, st>>>(X, a);
         else k_dyn_A<LP, false, MD><<<nb, 256, 0, st>>>(X, a);
     };
@@ -1533,6 +1605,10 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     // are its theta tendencies -- E forms none (k_dyn_E NTH) and B no flux for them (NOF)
     const bool ntu = !MD && in.ntu && !(rk0 && del4 && !a.d4o);
     const bool nth = !MD && in.nth;
+    // setup's edge copies (a.cp) by A instead of B, where B (RK0, NOF, NTU) would load u and ru for them alone
+    // and A runs in this call with the Smagorinsky gathers of u (undecomposed: A's cells own every edge but
+    // X_orph's); every other path keeps the copy in B
+    a.cpA = (!MD && a.cp && rk0 && ntu && nth && !et && !in.skipA && !S.halo && a.horiz_mixing == 0) ? 1 : 0;
     auto kB = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KE);
         if (!nb) return;
@@ -1555,6 +1631,12 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
                             decltype(Nt)::value><<<nb, 256, 0, st>>>(X, a);
                 };
                 auto go4 = [&](auto R, auto H, auto Di) {
+                    if constexpr (decltype(R)::value && !decltype(Di)::value) {
+                        if (a.cpA) {  // (the copies made by A: NCP)
+                            k_dyn_B<LP, true, false, decltype(H)::value, false, true, true, true><<<nb, 256, 0, st>>>(X, a);
+                            return;
+                        }
+                    }
                     if (nth && ntu) go(R, H, Di, T_{}, T_{});
                     else if (nth) go(R, H, Di, T_{}, F_{});
                     else go(R, H, Di, F_{}, T_{});
