@@ -143,7 +143,12 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * kernel, the stage's recover edge kernel); "mru" = 1 (default; the MPAS dynamics, fast path) has
  * the kernel forming a stage's final tend_u store its first acoustic substep's ru_p and ruAvg;
  * "msml" = 1 (default; the MPAS dynamics) applies each stage's set_smlstep in dyn_tend's cell
- * kernel.  "trepw" = 2 (speed only; measured within 2 %, default 1): two
+ * kernel.  "accoef" = 1 (default; speed only; mpas_atm_srk3 in the reference semantics, not with
+ * "tmedge"): the acoustic launches form cofwr, coftz and a_tri from the columns they hold (zz, theta_m,
+ * cofwz, cofwt) by vert_imp's own expressions instead of loading the stored columns, and stage 0's setup
+ * launch leaves the three unstored (stage 1's vert_imp stores them): every field after a step
+ * bit-identical; mpas_atm_advance_acoustic_step_work always reads the stored columns; a value other
+ * than 0 or 1: MPAS_EINVAL.  "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of
  * compact cell tiles in LDS and no edge scratch, when every cell has at most 6 edges with

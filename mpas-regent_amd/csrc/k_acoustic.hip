@@ -79,10 +79,19 @@ __global__ __launch_bounds__(256) void k_acoustic_orph(DevState S, double coefp)
 // SML (atm_srk3, option "fusesml"; a stage's first substep): the stage's set_smlstep first;
 // 1 from its slope fluxes, 2 (fast path) from their sum per level, X_smlS, formed once per step
 // by k_sml_flux: u_tend, zb_cell and zb3_cell do not change within a step (reference semantics)
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML>
+// ACO (atm_srk3, option "accoef", reference semantics): cofwr, coftz and a_tri are not loaded but formed
+// from zz, theta_m, cofwz and cofwt, which the body holds anyway, by vert_imp's own expressions
+// (k_cols.h vi_cofwr / vi_coftz / vi_a_tri: the same text and order, so the stored columns' bits) with
+// dtseps of the vert_imp call that formed the live set; coftz at level L is the field's kept value.
+// Valid while theta_m is what that call read: always in the reference semantics (nothing writes it
+// within the step).  The remaining columns are re-paired so that no half of a 16-B load is dead.
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO = false>
 __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int small_step, double epssm, double resm,
-                                              double coefp, int ncb, Blk bk, int wold = 1, int ddx = 0) {
+                                              double coefp, int ncb, Blk bk, int wold = 1, int ddx = 0,
+                                              double dtseps = 0.0) {
     static_assert(!(MPASV && MODE), "the deferred damping is the reference semantics' (physics 0)");
+    static_assert(!(MPASV && ACO), "the MPAS forms load the stored set (recover changes theta_m)");
+    static_assert(!(TME && ACO), "option tmedge keeps the stored set (its exact first launch would lose a wave)");
     static_assert(!SML || (FIRST && !MPASV), "set_smlstep precedes a stage's first substep (reference semantics)");
     static_assert(SML != 2 || !EXACT, "the flux sum reassociates: fast path only");
     const int L = S.L, k = (int)(threadIdx.x % LP);
@@ -167,7 +176,10 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         }
     }
     // (rup_ / ts_ at k >= L: unused, the flux sum below selects on kl)
-    col_rd2<LP>(fd(S, F_w), fd(S, F_coftz), c, k, L, w, coftz);
+    // (ACO: w with dss -- with rw under !ddx, below)
+    if constexpr (!ACO) col_rd2<LP>(fd(S, F_w), fd(S, F_coftz), c, k, L, w, coftz);
+    else if (ddx) col_rd2<LP>(fd(S, F_w), fd(S, F_dss), c, k, L, w, dss);
+    else col_rd2<LP>(fd(S, F_w), fd(S, F_rw), c, k, L, w, rw);
     col_rd2<LP>(fd(S, F_zz), fd(S, F_rho_zz), c, k, L, zz, rz);
     const double fzm = fd(S, F_fzm)[k], fzp = fd(S, F_fzp)[k];
     int wst = 0;  // SML: set_smlstep's w store (1: the new w, 2: the padding's 0.0), made below
@@ -226,22 +238,26 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     // the MPAS dynamics (physics = 2); the implicit Rayleigh term reads the state w
     const double tw = (MPASV && S.physics == 2) ? col_rd<LP>(fd(S, F_tend_w), c, k, L) : w;
     col_rd2<LP>(fd(S, F_cofwt), fd(S, F_cofwz), c, k, L, cofwt, cofwz);
-    col_rd2<LP>(fd(S, F_cofwr), fd(S, F_a_tri), c, k, L, cofwr, a_tri);
+    if constexpr (!ACO) col_rd2<LP>(fd(S, F_cofwr), fd(S, F_a_tri), c, k, L, cofwr, a_tri);
     // (ddx, atm_srk3 with option smlsum: rw_save - rw, the step uses only their difference, from
     // X_Dd -- formed once per step, the same value: one column read instead of two)
     double dd;
     if (!MPASV && ddx) {
         col_rd2<LP>(fd(S, F_alpha_tri), fd(S, X_Dd), c, k, L, alpha, dd);
-        dss = col_rd<LP>(fd(S, F_dss), c, k, L);
+        if constexpr (!ACO) dss = col_rd<LP>(fd(S, F_dss), c, k, L);
     } else {
         col_rd2<LP>(fd(S, F_alpha_tri), fd(S, F_rw_save), c, k, L, alpha, rws);
-        col_rd2<LP>(fd(S, F_rw), fd(S, F_dss), c, k, L, rw, dss);
+        if constexpr (!ACO) col_rd2<LP>(fd(S, F_rw), fd(S, F_dss), c, k, L, rw, dss);
+        else dss = col_rd<LP>(fd(S, F_dss), c, k, L);
         dd = rws - rw;
     }
     double gam = 0.0, tend_th = 0.0;
     if constexpr (MPASV) col_rd2<LP>(fd(S, F_gamma_tri), fd(S, F_tend_theta), c, k, L, gam, tend_th);
     const double tt = MPASV ? tend_th : tm;  // tend_rt: the reference reads theta_m (Q8)
     const double cofrz = fd(S, F_cofrz)[k], rdzw = fd(S, F_rdzw)[k];
+    // (ACO: coftz's kept level L with the loads; the three values are formed below, where they are used)
+    double coftz_L = 0.0;
+    if constexpr (ACO) coftz_L = keepv<LP>(S, F_coftz, KC, c);
     // ---- the stores of the values formed above (the previous substep's damped ru_p on the
     // edges this cell owns, set_smlstep's w), after the column's last load: made where they
     // were formed, they let no later load move above them (the compiler cannot tell they do not
@@ -320,6 +336,15 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         double flux = sgn[i] * dts * cdv[i] * ldz(kl, rpe) * invA;
         rs = sub_if(kl, rs, flux);
         ts = sub_if(kl, ts, flux * 0.5 * (ldz(kl, colk(tm_f, cc2[i])) + ldz(kl, colk(tm_f, cc1[i]))));
+    }
+    if constexpr (ACO) {
+        // vi_column's values at 0 < k < L, the levels the step uses them at (coftz also at level 0,
+        // 0.0, and at level L, the kept value, for coftz_p of level L - 1)
+        const bool in = k >= 1 && k < L;
+        const double zz_dn = lvl_dn<LP>(zz, k), tm_dn = lvl_dn<LP>(tm, k), rdzw_dn = lvl_dn<LP>(rdzw, k);
+        cofwr = in ? vi_cofwr(dtseps, fzm, fzp, zz, zz_dn) : 0.0;
+        coftz = in ? vi_coftz(dtseps, fzm, fzp, tm, tm_dn) : (k == L ? coftz_L : 0.0);
+        a_tri = vi_a_tri(cofwz, lvl_dn<LP>(coftz, k), rdzw_dn, zz_dn, cofwr, dtseps * rdzw_dn, lvl_dn<LP>(cofwt, k));
     }
     // ---- rs, ts (:1657-1658) from the OLD rw_p
     const double rwp_p = lvl_up<LP>(rwp, k), coftz_p = lvl_up<LP>(coftz, k);
@@ -468,36 +493,37 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     }
     store_div(rtp_new);
 }
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML>
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO>
 __global__ __launch_bounds__(256) void k_acoustic(DevState S, double dts, int small_step, double epssm, double resm,
-                                                 double coefp, int ncb, int wold, int ddx) {
-    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                this_blk(), wold, ddx);
+                                                 double coefp, int ncb, int wold, int ddx, double dtseps) {
+    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
+                                                                     this_blk(), wold, ddx, dtseps);
 }
 // MODE 2 on a small grid (fewer than kTailCells owned cells, where a launch's fixed cost is
 // most of its time): the orphan edges' blocks at the tail of the cell grid, one launch
 // instead of two (on large grids the separate launch keeps the cell path's mesh rows in
 // scalar loads, profiles/r04/orph_split)
 constexpr int kTailCells = 16384;
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool TME, int SML>
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool TME, int SML, bool ACO>
 __global__ __launch_bounds__(256) void k_acoustic_o(DevState S, double dts, int small_step, double epssm, double resm,
-                                                   double coefp, int ncb, int wold, int ddx) {
+                                                   double coefp, int ncb, int wold, int ddx, double dtseps) {
     const int b = (int)blockIdx.x;
     if (b < ncb)
-        acoustic_body<LP, EXACT, SELF, FIRST, false, 2, TME, SML>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                   Blk{b, ncb}, wold, ddx);
+        acoustic_body<LP, EXACT, SELF, FIRST, false, 2, TME, SML, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
+                                                                        Blk{b, ncb}, wold, ddx, dtseps);
     else acoustic_orph_body<LP, TME>(S, coefp, b - ncb);
 }
 // option "hfuse" (atm_srk3, stages 0 and 1): a stage's last acoustic launch (MODE 2, the
 // damping of the previous substep inside) beside the stage's solve_diagnostics vertex /
 // cell kernel, which reads u only -- nothing the acoustic step reads or writes
-template <int LP, bool EXACT, bool SELF, int EPW>
+template <int LP, bool EXACT, bool SELF, int EPW, bool ACO>
 __global__ __launch_bounds__(256) void k_hf_ac_vc(DevState S, double dts, int small_step, double epssm, double resm,
-                                                 double coefp, int ncb, int nb1, int nVB, int wold, int ddx) {
+                                                 double coefp, int ncb, int nb1, int nVB, int wold, int ddx,
+                                                 double dtseps) {
     const int b = (int)blockIdx.x;
     if (b < ncb)
-        acoustic_body<LP, EXACT, SELF, false, false, 2, false, false>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                       Blk{b, ncb}, wold, ddx);
+        acoustic_body<LP, EXACT, SELF, false, false, 2, false, false, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
+                                                                            Blk{b, ncb}, wold, ddx, dtseps);
     else if (b < nb1) acoustic_orph_body<LP, false>(S, coefp, b - ncb);
     else solve_vc_body<LP, EPW, false>(S, nVB, 0, Blk{b - nb1, (int)gridDim.x - nb1});
 }
@@ -581,7 +607,10 @@ __global__ __launch_bounds__(256) void k_acoustic_ru(DevState S, double dts, int
 
 template <int LP>
 static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int small_step, int exact, int mode,
-                              double coef_prev, int tme, int sml, int wold, int ddx, int mdamp, int rudone) {
+                              double coef_prev, int tme, int sml, int wold, int ddx, int mdamp, int rudone, int aco,
+                              double dts_vi) {
+    if (aco && (S.physics || tme)) return hipErrorInvalidValue;  // (the MPAS forms and tmedge load the stored set)
+    const double dtseps = aco ? vi_dtseps(dts_vi) : 0.0;
     if ((tme && (S.physics || S.halo)) || (sml && S.physics)) return hipErrorInvalidValue;  // (atm_srk3, reference semantics)
     if (mdamp && (!S.physics || small_step == 0)) return hipErrorInvalidValue;
     if (rudone && (S.physics != 2 || small_step != 0)) return hipErrorInvalidValue;
@@ -617,10 +646,11 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
         const int grid = ncb;
         const bool first = small_step == 0;
         if (tail) {  // (one launch: the orphan edges' blocks after the cell blocks)
-            auto go_t = [&](auto ex, auto sf) {
-                constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value;
-#define MPAS_ACO(FI, TM, SM) \
-    k_acoustic_o<LP, E, SF, FI, TM, SM><<<ncb + nob, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, ncb, wold, ddx)
+            auto go_t = [&](auto ex, auto sf, auto ac) {
+                constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value, A = decltype(ac)::value;
+#define MPAS_ACO(FI, TM, SM)                                                                                        \
+    k_acoustic_o<LP, E, SF, FI, TM, SM, (A && !(TM))><<<ncb + nob, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, ncb, \
+                                                                      wold, ddx, dtseps)
                 if (first) {
                     if constexpr (!E) {
                         if (sml == 2) {
@@ -636,19 +666,25 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
                 }
 #undef MPAS_ACO
             };
-            auto go_ts = [&](auto ex) {
-                if (X.selfc) go_t(ex, std::true_type{});
-                else go_t(ex, std::false_type{});
+            auto go_ts = [&](auto ex, auto ac) {
+                if (X.selfc) go_t(ex, std::true_type{}, ac);
+                else go_t(ex, std::false_type{}, ac);
             };
-            if (exact) go_ts(std::true_type{});
-            else go_ts(std::false_type{});
+            auto go_ta = [&](auto ex) {
+                if (aco) go_ts(ex, std::true_type{});
+                else go_ts(ex, std::false_type{});
+            };
+            if (exact) go_ta(std::true_type{});
+            else go_ta(std::false_type{});
             return;
         }
-        auto go = [&](auto ex, auto sf, auto md) {
-            constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value;
+        auto go = [&](auto ex, auto sf, auto md, auto ac) {
+            constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value, A = decltype(ac)::value;
             constexpr int M = decltype(md)::value;
-#define MPAS_AC(FI, MP, MM, TM, SM) \
-    k_acoustic<LP, E, SF, FI, MP, MM, TM, SM><<<grid, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, ncb, wold, ddx)
+            // (ACO: never with the MPAS forms or tmedge -- refused above)
+#define MPAS_AC(FI, MP, MM, TM, SM)                                                                                 \
+    k_acoustic<LP, E, SF, FI, MP, MM, TM, SM, (A && !(MP) && !(TM))><<<grid, 256, 0, st>>>(              \
+        X, dts, small_step, epssm, resm, coef_prev, ncb, wold, ddx, dtseps)
             if constexpr (M == 0) {
                 if (X.physics) {
                     if (first) MPAS_AC(true, true, 0, false, false);
@@ -674,17 +710,21 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
             }
 #undef MPAS_AC
         };
-        auto go_m = [&](auto ex, auto sf) {
-            if (mode == 1) go(ex, sf, std::integral_constant<int, 1>{});
-            else if (mode == 2) go(ex, sf, std::integral_constant<int, 2>{});
-            else go(ex, sf, std::integral_constant<int, 0>{});
+        auto go_m = [&](auto ex, auto sf, auto ac) {
+            if (mode == 1) go(ex, sf, std::integral_constant<int, 1>{}, ac);
+            else if (mode == 2) go(ex, sf, std::integral_constant<int, 2>{}, ac);
+            else go(ex, sf, std::integral_constant<int, 0>{}, ac);
         };
-        auto go_s = [&](auto ex) {
-            if (X.selfc) go_m(ex, std::true_type{});
-            else go_m(ex, std::false_type{});
+        auto go_s = [&](auto ex, auto ac) {
+            if (X.selfc) go_m(ex, std::true_type{}, ac);
+            else go_m(ex, std::false_type{}, ac);
         };
-        if (exact) go_s(std::true_type{});
-        else go_s(std::false_type{});
+        auto go_a = [&](auto ex) {
+            if (aco) go_s(ex, std::true_type{});
+            else go_s(ex, std::false_type{});
+        };
+        if (exact) go_a(std::true_type{});
+        else go_a(std::false_type{});
         if (mode == 2 && nob) {
             if (tme) k_acoustic_orph<LP, true><<<nob, 256, 0, st>>>(X, coef_prev);
             else k_acoustic_orph<LP, false><<<nob, 256, 0, st>>>(X, coef_prev);
@@ -707,32 +747,41 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
     return hipGetLastError();
 }
 hipError_t launch_acoustic(const DevState& S, hipStream_t st, double dts, int small_step, int exact, int mode,
-                           double coef_prev, int tme, int sml, int wold, int ddx, int mdamp, int rudone) {
+                           double coef_prev, int tme, int sml, int wold, int ddx, int mdamp, int rudone, int aco,
+                           double dts_vi) {
     MPAS_LP_DISPATCH(S.LP, acoustic_lp, S, st, dts, small_step, exact, mode, coef_prev, tme, sml, wold, ddx, mdamp,
-                     rudone);
+                     rudone, aco, dts_vi);
 }
 template <int LP>
 static hipError_t hf_ac_vc_lp(const DevState& S, hipStream_t st, double dts, int small_step, int exact,
-                              double coef_prev, int wold, int ddx) {
+                              double coef_prev, int wold, int ddx, int aco, double dts_vi) {
     if (S.physics || S.halo || small_step == 0 || S.epw != 2) return hipErrorInvalidValue;
     const double epssm = kEpssm, resm = (1.0 - epssm) / (1.0 + epssm);
+    const double dtseps = aco ? vi_dtseps(dts_vi) : 0.0;
     const int ncb = col_blocks<LP>(S, KC);
     const int nb1 = ncb + (S.n_orph + 256 / LP - 1) / (256 / LP);
     const int nv = col_blocks_n<LP, 2>(S, KV), nb2 = nv + col_blocks_n<LP, 2>(S, KC);
     if (!ncb || !nb2) return hipErrorInvalidValue;
     const int grid = nb1 + nb2;
-    if (exact) {
-        if (S.selfc) k_hf_ac_vc<LP, true, true, 2><<<grid, 256, 0, st>>>(S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx);
-        else k_hf_ac_vc<LP, true, false, 2><<<grid, 256, 0, st>>>(S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx);
-    } else {
-        if (S.selfc) k_hf_ac_vc<LP, false, true, 2><<<grid, 256, 0, st>>>(S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx);
-        else k_hf_ac_vc<LP, false, false, 2><<<grid, 256, 0, st>>>(S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx);
-    }
+    auto go = [&](auto ex, auto sf, auto ac) {
+        k_hf_ac_vc<LP, decltype(ex)::value, decltype(sf)::value, 2, decltype(ac)::value><<<grid, 256, 0, st>>>(
+            S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx, dtseps);
+    };
+    auto go_a = [&](auto ex, auto sf) {
+        if (aco) go(ex, sf, std::true_type{});
+        else go(ex, sf, std::false_type{});
+    };
+    auto go_s = [&](auto ex) {
+        if (S.selfc) go_a(ex, std::true_type{});
+        else go_a(ex, std::false_type{});
+    };
+    if (exact) go_s(std::true_type{});
+    else go_s(std::false_type{});
     return hipGetLastError();
 }
 hipError_t launch_hf_acoustic_solve_vc(const DevState& S, hipStream_t st, double dts, int small_step, int exact,
-                                       double coef_prev, int wold, int ddx) {
-    MPAS_LP_DISPATCH(S.LP, hf_ac_vc_lp, S, st, dts, small_step, exact, coef_prev, wold, ddx);
+                                       double coef_prev, int wold, int ddx, int aco, double dts_vi) {
+    MPAS_LP_DISPATCH(S.LP, hf_ac_vc_lp, S, st, dts, small_step, exact, coef_prev, wold, ddx, aco, dts_vi);
 }
 
 }  // namespace mpas

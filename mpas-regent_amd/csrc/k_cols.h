@@ -38,15 +38,34 @@ __device__ __forceinline__ void st64k(double* d, size_t i, double2 v, Pair64 q, 
 }
 
 // ---------------------------------------------------------------- vert_imp
+// The three coefficients that are functions of columns the acoustic step holds in registers
+// anyway (zz, theta_m, cofwz, cofwt and the per-level arrays): vi_column forms and stores them,
+// acoustic_body (option "accoef") forms them again instead of loading the stored columns.  One
+// text, so one operation order: with -ffp-contract=off the same bits (tests/test_accoef_identity.py).
+// The _m arguments are the values of level k - 1; used at 0 < k < L.
+__device__ __forceinline__ double vi_cofwr(double dtseps, double fzm, double fzp, double zz, double zz_m) {
+    return .5 * dtseps * kGravity * (fzm * zz + fzp * zz_m);
+}
+__device__ __forceinline__ double vi_coftz(double dtseps, double fzm, double fzp, double tm, double tm_m) {
+    return dtseps * (fzm * tm + fzp * tm_m);
+}
+__device__ __forceinline__ double vi_a_tri(double cofwz, double coftz_m, double rdzw_m, double zz_m, double cofwr,
+                                           double cofrz_m, double cofwt_m) {
+    return -1.0 * cofwz * coftz_m * rdzw_m * zz_m + cofwr * cofrz_m - cofwt_m * coftz_m * rdzw_m;
+}
+
 // one column of atm_compute_vert_imp_coefs from its loaded inputs (k_vert_imp, and the
 // stage-0 fusion with the setup copies and the moist coefficients, k_setup_vi)
 template <int LP, bool MPASV>
 __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, double zz, double exner, double tm, double cqw,
                                           double qtot, double rb, double rtb, double rtp, double exb, double gamma_old,
                                           double coftz_old, double dtseps, double rcv, double c2, bool live = true,
-                                          bool nbc = false) {
+                                          bool nbc = false, bool nco = false) {
     // (nbc, atm_srk3 option ntu: stage 0's vert_imp -- b_tri and c_tri are dead there: stage 1's vert_imp
     // rewrites both and no task reads them in between, nor does that vert_imp; not stored)
+    // (nco, atm_srk3 option accoef: stage 0's vert_imp -- cofwr, coftz and a_tri are dead there too: only the
+    // acoustic step reads them, it forms them itself, and stage 1's vert_imp stores all three; not stored)
+    // (coftz_old: the kept value of coftz at lane L, for coftz_p of level L - 1; any value elsewhere)
     const int L = S.L;
     const double *fzm_a = fd(S, F_fzm), *fzp_a = fd(S, F_fzp), *rdzu_a = fd(S, F_rdzu), *rdzw_a = fd(S, F_rdzw);
     const double fzm = fzm_a[k], fzp = fzp_a[k], rdzu = rdzu_a[k], rdzw = rdzw_a[k];
@@ -56,11 +75,11 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     // :550-564
     double cofwr = 0.0, cofwz = 0.0, coftz = coftz_old, cofwt = 0.0;
     if (k < L) {
-        if (k > 0) cofwr = .5 * dtseps * kGravity * (fzm * zz + fzp * zz_m);
+        if (k > 0) cofwr = vi_cofwr(dtseps, fzm, fzp, zz, zz_m);
         coftz = 0.0;
         if (k > 0) {
             cofwz = dtseps * c2 * (fzm * zz + fzp * zz_m) * rdzu * cqw * (fzm * exner + fzp * exner_m);
-            coftz = dtseps * (fzm * tm + fzp * tm_m);
+            coftz = vi_coftz(dtseps, fzm, fzp, tm, tm_m);
         }
         double qtotal = qtot;
         cofwt = .5 * dtseps * rcv * zz * kGravity * rb / (1.0 + qtotal) * exner / ((rtb + rtp) * exb);
@@ -72,7 +91,7 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     const double cofrz = dtseps * rdzw, cofrz_m = dtseps * rdzw_m;      // :537-539
 
     // :566-578 (every lane; used at 0 < k < L)
-    const double a = -1.0 * cofwz * coftz_m * rdzw_m * zz_m + cofwr * cofrz_m - cofwt_m * coftz_m * rdzw_m;
+    const double a = vi_a_tri(cofwz, coftz_m, rdzw_m, zz_m, cofwr, cofrz_m, cofwt_m);
     const double b = MPASV ? 1.0 + cofwz * (coftz * rdzw * zz + coftz * rdzw_m * zz_m) -
                                  coftz * (cofwt * rdzw - cofwt_m * rdzw_m) + cofwr * ((cofrz - cofrz_m))
                            : 1.0 + cofwz * (coftz * rdzw * zz + coftz * rdzw_m * zz_m) -
@@ -119,14 +138,23 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     // written with their kept values: keep tails, mpas_dev.h; every line of a column whole)
     auto kL = [&](int f) { return keepv<LP>(S, f, KC, c); };
     auto k0 = [&](int f) { return keepv<LP>(S, f, KC, c, true); };
-    put2<LP>(fw(S, F_coftz), c, fw(S, F_cofwt), c, k, KEEPW(coftz, kL(F_coftz)), KEEPW(cofwt, kL(F_cofwt)), live, live);
-    put2<LP>(fw(S, F_cofwr), c, fw(S, F_cofwz), c, k, KEEPW0(cofwr, k0(F_cofwr), kL(F_cofwr)),
-             KEEPW0(cofwz, k0(F_cofwz), kL(F_cofwz)), live, live);
+    if (nco) {  // (the two coefficients the acoustic step still loads, paired)
+        put2<LP>(fw(S, F_cofwt), c, fw(S, F_cofwz), c, k, KEEPW(cofwt, kL(F_cofwt)),
+                 KEEPW0(cofwz, k0(F_cofwz), kL(F_cofwz)), live, live);
+    } else {
+        put2<LP>(fw(S, F_coftz), c, fw(S, F_cofwt), c, k, KEEPW(coftz, kL(F_coftz)), KEEPW(cofwt, kL(F_cofwt)), live, live);
+        put2<LP>(fw(S, F_cofwr), c, fw(S, F_cofwz), c, k, KEEPW0(cofwr, k0(F_cofwr), kL(F_cofwr)),
+                 KEEPW0(cofwz, k0(F_cofwz), kL(F_cofwz)), live, live);
+    }
     if (nbc) {
         if (live) {
-            colk(fw(S, F_a_tri), c) = KEEPW0(a, k0(F_a_tri), kL(F_a_tri));
+            if (!nco) colk(fw(S, F_a_tri), c) = KEEPW0(a, k0(F_a_tri), kL(F_a_tri));
             colk(fw(S, F_alpha_tri), c) = KEEPW0(alpha, k0(F_alpha_tri), kL(F_alpha_tri));
         }
+    } else if (nco) {
+        if (live) colk(fw(S, F_b_tri), c) = KEEPW0(b, k0(F_b_tri), kL(F_b_tri));
+        put2<LP>(fw(S, F_c_tri), c, fw(S, F_alpha_tri), c, k, KEEPW0(cc, k0(F_c_tri), kL(F_c_tri)),
+                 KEEPW0(alpha, k0(F_alpha_tri), kL(F_alpha_tri)), live, live);
     } else {
         put2<LP>(fw(S, F_a_tri), c, fw(S, F_b_tri), c, k, KEEPW0(a, k0(F_a_tri), kL(F_a_tri)),
                  KEEPW0(b, k0(F_b_tri), kL(F_b_tri)), live, live);
@@ -151,7 +179,9 @@ __device__ __forceinline__ void vert_imp_body(const DevState& S, double dtseps, 
     gather2<LP>(fd(S, F_qtot), c, fd(S, F_rho_base), c, k, qtot, rb);
     gather2<LP>(fd(S, F_rtheta_base), c, fd(S, F_rtheta_p), c, k, rtb, rtp);
     gather2<LP>(fd(S, F_exner_base), c, fd(S, F_gamma_tri), c, k, exb, gamma_old);
-    const double coftz_old = colk(fd(S, F_coftz), c);  // level L keeps its (never written) value
+    // (level L of coftz keeps its never-written value: the field's keep tail holds it; lane L alone
+    // needs it, for coftz_p of level L - 1 -- the column is not loaded)
+    const double coftz_old = k == S.L ? keepv<LP>(S, F_coftz, KC, c) : 0.0;
     vi_column<LP, MPASV>(S, c, k, zz, exner, tm, cqw, qtot, rb, rtb, rtp, exb, gamma_old, coftz_old, dtseps, rcv, c2,
                          live);
 }
@@ -556,7 +586,7 @@ __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double
     gather2<LP>(fd(S, F_zz), c, fd(S, F_exner), c, k, zz, exner);
     gather2<LP>(fd(S, F_rho_base), c, fd(S, F_rtheta_base), c, k, rb, rtb);
     gather2<LP>(fd(S, F_exner_base), c, fd(S, F_gamma_tri), c, k, exb, gamma_old);
-    const double coftz_old = colk(fd(S, F_coftz), c);
+    const double coftz_old = k == L ? keepv<LP>(S, F_coftz, KC, c) : 0.0;  // (as vert_imp_body)
     // :773-777 the save copies (every level but L; padding levels carry zeros either way)
     // (level L: the kept values, keep tails in mpas_dev.h -- every line of a column whole)
     auto kL = [&](int f) { return keepv<LP>(S, f, KC, c); };
@@ -576,6 +606,7 @@ __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double
              KEEPW0(cqw, keepv<LP>(S, F_cqw, KC, c, true), kL(F_cqw)), live, live);
     // (cqw is used at 0 < k < L only, qtot at k < L: the values just written)
     vi_column<LP, MPASV>(S, c, k, zz, exner, tm, cqw, qtot, rb, rtb, rtp, exb, gamma_old, coftz_old, dtseps, rcv, c2,
-                         live, (copies & 2) != 0);  // (copies bit 1: b_tri / c_tri dead, atm_srk3 option ntu)
+                         live, (copies & 2) != 0,   // (copies bit 1: b_tri / c_tri dead, atm_srk3 option ntu)
+                         (copies & 4) != 0);        // (bit 2: cofwr / coftz / a_tri dead, option accoef)
 }
 }  // namespace mpas

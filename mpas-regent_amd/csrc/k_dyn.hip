@@ -1875,7 +1875,7 @@ static hipError_t hf_e_A_lp(const DevState& S, hipStream_t st, const DynTendArgs
     if (S.halo || S.physics || S.epw != 2) return hipErrorInvalidValue;
     const DynK a = make_dynk(S, next);
     const bool rk0 = a.rk_step == 0;
-    const double dtseps = .5 * dts_vi * (1.0 + kEpssm), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
+    const double dtseps = vi_dtseps(dts_vi), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
     const int nb1 = col_blocks_n<LP, 2>(S, KE), nb2 = vi ? col_blocks<LP>(S, KC) : 0, nb3 = col_blocks<LP>(S, KC);
     if (!nb1 || !nb3) return hipErrorInvalidValue;
     const int grid = nb1 + nb2 + nb3;
@@ -1911,7 +1911,7 @@ static hipError_t hf_setup_A_lp(const DevState& S, hipStream_t st, const DynTend
                                 int flux) {
     if (S.halo || S.physics) return hipErrorInvalidValue;
     const DynK a = make_dynk(S, stage0);
-    const double dtseps = .5 * dts * (1.0 + kEpssm), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
+    const double dtseps = vi_dtseps(dts), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
     const int ncb = col_blocks<LP>(S, KC), nb1 = ncb + (edges ? col_blocks<LP>(S, KE) : 0);
     if (!ncb) return hipErrorInvalidValue;
     const int nb = nb1 + ncb * (flux ? 2 : 1);

@@ -211,7 +211,7 @@ hipError_t launch_hf_solve_e_finish(const DevState& S, hipStream_t st, int recon
 template <int LP>
 static hipError_t hf_e_vi_lp(const DevState& S, hipStream_t st, double dts) {
     if (!hf_ok(S)) return hipErrorInvalidValue;
-    const double dtseps = .5 * dts * (1.0 + kEpssm), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
+    const double dtseps = vi_dtseps(dts), rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
     epw_go<LP>(S, [&](auto epw) {
         constexpr int E = decltype(epw)::value;
         const int nb1 = col_blocks_n<LP, E>(S, KE), nb2 = col_blocks<LP>(S, KC);

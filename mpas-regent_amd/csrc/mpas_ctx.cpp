@@ -119,6 +119,9 @@ struct mpas_ctx {
     int ntu = 1;       // option "ntu" (with defer4): that rk_step 0 call's whole tend_u is dead (the next stage's
                        // edge kernel rewrites it, no task in between reads it): its edge kernel forms none of
                        // it and skips its gathers (k_dyn_B NTU; the same values of everything read later)
+    int accoef = 1;    // option "accoef" (atm_srk3, reference semantics): the acoustic launches form cofwr, coftz
+                       // and a_tri from the columns they hold instead of loading them; stage 0's setup launch
+                       // does not store the three, vert_imp takes coftz's level L from the keep tail (same bits)
     int fusedamp = 1;  // option "fusedamp": atm_srk3 applies each divergence damping inside the next
                        // acoustic launch (reference semantics, undecomposed; same bits)
     void* raw[X_COUNT] = {};  // the allocations behind S.f (S.f[f] = raw[f] + stagger)
@@ -1008,6 +1011,13 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         if (c->msml && S.physics == 2) a.smlE = 1;
         return a;
     };
+    // option accoef (reference semantics, where nothing writes theta_m within the step): every acoustic
+    // launch forms cofwr / coftz / a_tri itself, with the dts of the setup or vert_imp launch that formed
+    // the live coefficient set (dts_vi, recorded at each of those launches -- not the acoustic launch's own)
+    // (not with option tmedge, off by default: its launches keep loading the stored set -- the exact first
+    // launch of that form would lose a wave of occupancy to the three expressions, profiles/r08)
+    const int aco = (c->accoef && S.physics == 0 && !tme) ? 1 : 0;
+    double dts_vi = 0.0;
     bool flux_done = false;  // (option smlsum: the step's flux sum, beside setup and A on small grids)
     // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
     // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
@@ -1020,6 +1030,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         run_task(c, smls ? "hfuse[setup+dyn_A+sml_flux]" : "hfuse[setup+dyn_A]", [&] {
             return launch_hf_setup_dyn_A(S, st, stage_args(0), rk_sub_timestep[0], fcopy ? 0 : 1, smls ? 1 : 0);
         });
+        dts_vi = rk_sub_timestep[0];
         a_done = true;
         flux_done = smls;
     } else if (c->fusesetup) {  // :404-417 as one column-local launch (same values; MPAS forms under physics)
@@ -1028,17 +1039,21 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         const bool nbc = c->ntu == 1 || c->ntu == 2;
         run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
                           : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
-                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0); });
+                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco); });
+        dts_vi = rk_sub_timestep[0];
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
         run_task(c, "atm_compute_moist_coefficients", [&] { return launch_moist_coefficients(S, st); });
         run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[0]); });
+        dts_vi = rk_sub_timestep[0];
     }
     if (smls && !flux_done)
         run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st); });
     for (int rk_step = 0; rk_step < 3; rk_step++) {  // :426-477
-        if (rk_step == 1 && !vi_done)
+        if (rk_step == 1 && !vi_done) {
             run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[rk_step]); });
+            dts_vi = rk_sub_timestep[rk_step];
+        }
         DynTendArgs a = stage_args(rk_step);
         a.skipA = a_done ? 1 : 0;
         // option vdyn (reference semantics): the last stage's v (:429-437) is reconstructed by its
@@ -1073,7 +1088,8 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                 const int wold = ((done_acoustic + 1 == n_acoustic) ? 1 : 0) | nst;
                 if (hf2 && rk_step < 2 && mode == 2 && small_step > 0 && small_step == n_small - 1) {
                     run_task(c, nst ? "hfuse[acoustic-st+solve_vc]" : "hfuse[acoustic+solve_vc]", [&] {
-                        return launch_hf_acoustic_solve_vc(S, st, dts, small_step, c->exact, coef_prev, wold, smls ? 1 : 0);
+                        return launch_hf_acoustic_solve_vc(S, st, dts, small_step, c->exact, coef_prev, wold, smls ? 1 : 0,
+                                                           aco, dts_vi);
                     });
                     vc_done = true;
                 } else {
@@ -1083,7 +1099,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                                                : std::string(acoustic_name(small_step, pending, sm, !(wold & 1)));
                     run_task(c, an.c_str(),
                              [&] { return launch_acoustic(S, st, dts, small_step, c->exact, mode, coef_prev, tme, sm, wold,
-                                                          smls ? 1 : 0); });
+                                                          smls ? 1 : 0, 0, 0, aco, dts_vi); });
                 }
                 if (mode == 2) fb.swap_rup();
                 fb.swap_dv();  // this substep's div is read next from X_dvB
@@ -1113,7 +1129,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
             const std::string anw = (small_step == 0 && ru_done) ? an1.substr(0, an1.size() - 1) + "-ru]" : an1;
             run_task(c, anw.c_str(), [&] {
                 return launch_acoustic(S, st, dts, small_step, c->exact, 0, cprev, tme, 0, nww ? 3 : 1, 0, mdp,
-                                       (small_step == 0 && ru_done) ? 1 : 0);
+                                       (small_step == 0 && ru_done) ? 1 : 0, aco, dts_vi);
             });
             if (!md_fold)
                 run_task(c, "atm_divergence_damping_3d", [&] { return launch_div_damping(S, st, dts, small_step == 0); });
@@ -1150,6 +1166,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                 return launch_hf_solve_e_dyn_A(S, st, nx, rk_step == 0 ? 1 : 0, rk_sub_timestep[1]);
             });
             if (rk_step == 0) vi_done = true;
+            if (rk_step == 0) dts_vi = rk_sub_timestep[1];
             a_done = true;
             vc_done = false;
         } else if (rk_step == 0 && solve0_dead) {
@@ -1161,6 +1178,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
             run_task(c, "hfuse[solve_e+vert_imp]",
                      [&] { return launch_hf_solve_e_vert_imp(S, st, rk_sub_timestep[1]); });
             vi_done = true;
+            dts_vi = rk_sub_timestep[1];
         } else {
             const int nv = (rk_step == 2 && vdyn_on) ? 1 : 0;
             // option ntu: a call before the last stage's, the next stage at rk_step > 0, stores only what
@@ -1471,6 +1489,10 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         else if (name && std::strcmp(name, "defer4") == 0) c->defer4 = value ? 1 : 0;
         else if (name && std::strcmp(name, "ntu") == 0) c->ntu = value < 0 ? 0 : value > 3 ? 3 : value;
         else if (name && std::strcmp(name, "mdamp") == 0) c->mdamp = value ? 1 : 0;
+        else if (name && std::strcmp(name, "accoef") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "accoef must be 0 or 1"};
+            c->accoef = (int)value;
+        }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
         else if (name && std::strcmp(name, "vdyn") == 0) c->vdyn = value ? 1 : 0;
@@ -1642,6 +1664,7 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "defer4") == 0) *value = c->defer4;
         else if (name && std::strcmp(name, "ntu") == 0) *value = c->ntu;
         else if (name && std::strcmp(name, "mdamp") == 0) *value = c->mdamp;
+        else if (name && std::strcmp(name, "accoef") == 0) *value = c->accoef;
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;
         else if (name && std::strcmp(name, "vdyn") == 0) *value = c->vdyn;

@@ -239,14 +239,20 @@ inline int col_blocks_n(const DevState& S, int kind) {
 hipError_t launch_rk_integration_setup(const DevState& S, hipStream_t st);
 hipError_t launch_moist_coefficients(const DevState& S, hipStream_t st);
 hipError_t launch_vert_imp_coefs(const DevState& S, hipStream_t st, double dts);
+// vert_imp's dtseps for a call with dts (:535), the one host expression of every launcher that forms
+// the coefficient set and of the acoustic launches that form three of its columns again (option accoef)
+inline double vi_dtseps(double dts) { return .5 * dts * (1.0 + kEpssm); }
 // setup + moist + vert_imp(dts) in one launch (option "fusesetup", reference semantics)
 // (nbc, atm_srk3 option ntu: vert_imp's b_tri / c_tri not stored -- stage 1's vert_imp rewrites them)
-hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges = true, int nbc = 0);
+// (nco, atm_srk3 option accoef, reference semantics: nor cofwr / coftz / a_tri -- the acoustic launches
+// of the step form them, and stage 1's vert_imp stores all three)
+hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges = true, int nbc = 0,
+                                       int nco = 0);
 // option hfuse (atm_srk3, reference semantics, undecomposed): a stage's last acoustic launch
 // (mode 2) beside its solve_diagnostics vertex / cell kernel; the stage's solve_diagnostics
 // edge kernel beside the next stage's dyn_tend A (and stage 1's vert_imp after stage 0)
 hipError_t launch_hf_acoustic_solve_vc(const DevState& S, hipStream_t st, double dts, int small_step, int exact,
-                                       double coef_prev, int wold = 1, int ddx = 0);
+                                       double coef_prev, int wold = 1, int ddx = 0, int aco = 0, double dts_vi = 0.0);
 hipError_t launch_hf_solve_e_dyn_A(const DevState& S, hipStream_t st, const DynTendArgs& next, int vi, double dts_vi);
 // ... and stage 0's setup + moist + vert_imp launch (fusesetup) beside stage 0's dyn_tend A
 // flux: also set_smlstep's flux sum of the step (X_smlS; option smlsum)
@@ -268,7 +274,11 @@ hipError_t launch_set_smlstep(const DevState& S, hipStream_t st, int exact);
 hipError_t launch_acoustic(const DevState& S, hipStream_t st, double dts, int small_step, int exact, int mode = 0,
                            double coef_prev = 0.0, int tme = 0, int sml = 0, int wold = 1, int ddx = 0,
                            int mdamp = 0,   // (mdamp: the MPAS forms, the previous substep's damping folded in)
-                           int rudone = 0);  // (rudone: option mru -- this stage's dyn_tend stored ru_p / ruAvg)
+                           int rudone = 0,  // (rudone: option mru -- this stage's dyn_tend stored ru_p / ruAvg)
+                           // aco (atm_srk3 option accoef, reference semantics): cofwr, coftz and a_tri formed
+                           // from the columns in registers, not loaded; dts_vi: the dts of the vert_imp call
+                           // that formed the live coefficient set (not this launch's dts)
+                           int aco = 0, double dts_vi = 0.0);
 // X_smlS = the sum of set_smlstep's slope-flux terms per cell and level (atm_srk3 fast path,
 // once per step: u_tend / zb_cell / zb3_cell are not written within a step)
 hipError_t launch_sml_flux(const DevState& S, hipStream_t st);
