@@ -148,7 +148,20 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * cofwz, cofwt) by vert_imp's own expressions instead of loading the stored columns, and stage 0's setup
  * launch leaves the three unstored (stage 1's vert_imp stores them): every field after a step
  * bit-identical; mpas_atm_advance_acoustic_step_work always reads the stored columns; a value other
- * than 0 or 1: MPAS_EINVAL.  "trepw" = 2 (speed only; measured within 2 %, default 1): two
+ * than 0 or 1: MPAS_EINVAL.  "dd0" = 1 (default; speed only; mpas_atm_srk3 in the reference semantics):
+ * the acoustic launches take rw_save - rw, their only use of the two columns, as the constant 0.0 and
+ * load neither -- the step's setup stores rw_save = rw where the difference is read and no task of the
+ * step writes rw: every field after a step bit-identical for finite rw (where rw is not finite the
+ * reference's NaN from rw_save - rw no longer enters); mpas_atm_advance_acoustic_step_work always
+ * reads the stored columns; a value other than 0 or 1: MPAS_EINVAL.  "smlkeep" = 1 (default; speed
+ * only; with "smlsum", undecomposed contexts): set_smlstep's slope-flux sum is formed ahead of a
+ * step only when its inputs may have changed since it was last formed, not in every step.  Every
+ * call of this interface makes the next step form it again, except mpas_atm_srk3 / mpas_atm_timestep
+ * themselves and the calls that write no field and no option (mpas_download, mpas_sync,
+ * mpas_get_option, mpas_get_stream, mpas_timing_*, mpas_field_*, mpas_halo_stats, mpas_last_error,
+ * mpas_summarize_timestep): a changed u_tend / zb_cell / zb3_cell counts at the very next step.
+ * Device memory of a context written behind this interface is not seen.  A value other than 0 or
+ * 1: MPAS_EINVAL.  "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of
  * compact cell tiles in LDS and no edge scratch, when every cell has at most 6 edges with

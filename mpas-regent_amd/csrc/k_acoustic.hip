@@ -85,12 +85,20 @@ __global__ __launch_bounds__(256) void k_acoustic_orph(DevState S, double coefp)
 // dtseps of the vert_imp call that formed the live set; coftz at level L is the field's kept value.
 // Valid while theta_m is what that call read: always in the reference semantics (nothing writes it
 // within the step).  The remaining columns are re-paired so that no half of a 16-B load is dead.
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO = false>
+// DD0 (atm_srk3, option "dd0", reference semantics): rw_save - rw, the step's only use of the two columns, is
+// the constant 0.0 -- the step's setup stores rw_save = rw at the levels the difference is read at and no
+// task of the step writes rw -- so neither column is loaded, nor X_Dd; dss then pairs with alpha_tri (ACO: w
+// alone), no half of a 16-B load dead.  The expressions stay as written, with dd = 0.0 (0.0 - E is not -E for
+// E = +0.0; no contraction, no fast-math).  A template parameter, not a third value of the runtime ddx: the
+// kernels without it are then the ones they were, register for register
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO = false,
+          bool DD0 = false>
 __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int small_step, double epssm, double resm,
                                               double coefp, int ncb, Blk bk, int wold = 1, int ddx = 0,
                                               double dtseps = 0.0) {
     static_assert(!(MPASV && MODE), "the deferred damping is the reference semantics' (physics 0)");
     static_assert(!(MPASV && ACO), "the MPAS forms load the stored set (recover changes theta_m)");
+    static_assert(!(MPASV && DD0), "the MPAS forms' recover writes rw");
     static_assert(!(TME && ACO), "option tmedge keeps the stored set (its exact first launch would lose a wave)");
     static_assert(!SML || (FIRST && !MPASV), "set_smlstep precedes a stage's first substep (reference semantics)");
     static_assert(SML != 2 || !EXACT, "the flux sum reassociates: fast path only");
@@ -176,8 +184,9 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         }
     }
     // (rup_ / ts_ at k >= L: unused, the flux sum below selects on kl)
-    // (ACO: w with dss -- with rw under !ddx, below)
+    // (ACO: w with dss -- with rw under !ddx; alone under DD0, where dss pairs with alpha_tri, below)
     if constexpr (!ACO) col_rd2<LP>(fd(S, F_w), fd(S, F_coftz), c, k, L, w, coftz);
+    else if constexpr (DD0) w = col_rd<LP>(fd(S, F_w), c, k, L);
     else if (ddx) col_rd2<LP>(fd(S, F_w), fd(S, F_dss), c, k, L, w, dss);
     else col_rd2<LP>(fd(S, F_w), fd(S, F_rw), c, k, L, w, rw);
     col_rd2<LP>(fd(S, F_zz), fd(S, F_rho_zz), c, k, L, zz, rz);
@@ -242,7 +251,10 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     // (ddx, atm_srk3 with option smlsum: rw_save - rw, the step uses only their difference, from
     // X_Dd -- formed once per step, the same value: one column read instead of two)
     double dd;
-    if (!MPASV && ddx) {
+    if constexpr (DD0) {
+        col_rd2<LP>(fd(S, F_alpha_tri), fd(S, F_dss), c, k, L, alpha, dss);
+        dd = 0.0;
+    } else if (!MPASV && ddx) {
         col_rd2<LP>(fd(S, F_alpha_tri), fd(S, X_Dd), c, k, L, alpha, dd);
         if constexpr (!ACO) dss = col_rd<LP>(fd(S, F_dss), c, k, L);
     } else {
@@ -493,37 +505,37 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     }
     store_div(rtp_new);
 }
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO>
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO, bool DD0>
 __global__ __launch_bounds__(256) void k_acoustic(DevState S, double dts, int small_step, double epssm, double resm,
                                                  double coefp, int ncb, int wold, int ddx, double dtseps) {
-    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                     this_blk(), wold, ddx, dtseps);
+    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML, ACO, DD0>(S, dts, small_step, epssm, resm, coefp, ncb,
+                                                                          this_blk(), wold, ddx, dtseps);
 }
 // MODE 2 on a small grid (fewer than kTailCells owned cells, where a launch's fixed cost is
 // most of its time): the orphan edges' blocks at the tail of the cell grid, one launch
 // instead of two (on large grids the separate launch keeps the cell path's mesh rows in
 // scalar loads, profiles/r04/orph_split)
 constexpr int kTailCells = 16384;
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool TME, int SML, bool ACO>
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool TME, int SML, bool ACO, bool DD0>
 __global__ __launch_bounds__(256) void k_acoustic_o(DevState S, double dts, int small_step, double epssm, double resm,
                                                    double coefp, int ncb, int wold, int ddx, double dtseps) {
     const int b = (int)blockIdx.x;
     if (b < ncb)
-        acoustic_body<LP, EXACT, SELF, FIRST, false, 2, TME, SML, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                        Blk{b, ncb}, wold, ddx, dtseps);
+        acoustic_body<LP, EXACT, SELF, FIRST, false, 2, TME, SML, ACO, DD0>(S, dts, small_step, epssm, resm, coefp,
+                                                                             ncb, Blk{b, ncb}, wold, ddx, dtseps);
     else acoustic_orph_body<LP, TME>(S, coefp, b - ncb);
 }
 // option "hfuse" (atm_srk3, stages 0 and 1): a stage's last acoustic launch (MODE 2, the
 // damping of the previous substep inside) beside the stage's solve_diagnostics vertex /
 // cell kernel, which reads u only -- nothing the acoustic step reads or writes
-template <int LP, bool EXACT, bool SELF, int EPW, bool ACO>
+template <int LP, bool EXACT, bool SELF, int EPW, bool ACO, bool DD0>
 __global__ __launch_bounds__(256) void k_hf_ac_vc(DevState S, double dts, int small_step, double epssm, double resm,
                                                  double coefp, int ncb, int nb1, int nVB, int wold, int ddx,
                                                  double dtseps) {
     const int b = (int)blockIdx.x;
     if (b < ncb)
-        acoustic_body<LP, EXACT, SELF, false, false, 2, false, false, ACO>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                            Blk{b, ncb}, wold, ddx, dtseps);
+        acoustic_body<LP, EXACT, SELF, false, false, 2, false, false, ACO, DD0>(S, dts, small_step, epssm, resm, coefp,
+                                                                                 ncb, Blk{b, ncb}, wold, ddx, dtseps);
     else if (b < nb1) acoustic_orph_body<LP, false>(S, coefp, b - ncb);
     else solve_vc_body<LP, EPW, false>(S, nVB, 0, Blk{b - nb1, (int)gridDim.x - nb1});
 }
@@ -531,21 +543,30 @@ __global__ __launch_bounds__(256) void k_hf_ac_vc(DevState S, double dts, int sm
 // X_smlS for SML = 2 (atm_srk3 fast path, reference semantics; once per step): per cell and
 // level k <= L the sum over the cell's edges of set_smlstep's slope-flux terms (k_set_smlstep
 // and acoustic_body SML = 1: the same terms, summed instead of subtracted from w one by one)
-template <int LP>
+// DD (k_cols.h sml_flux_body): 0 also X_Dd = rw_save - rw, after the step's setup; 1 the same from rw
+// alone, ahead of the setup (option smlkeep without dd0); 2 no X_Dd (option dd0)
+template <int LP, int DD>
 __global__ __launch_bounds__(256) void k_sml_flux(DevState S) {
-    sml_flux_body<LP>(S, this_blk());
+    sml_flux_body<LP, DD>(S, this_blk());
 }
 template <int LP>
-static hipError_t sml_flux_lp(const DevState& S, hipStream_t st) {
+static hipError_t sml_flux_lp(const DevState& S, hipStream_t st, int dd) {
+    if (dd < 0 || dd > 2) return hipErrorInvalidValue;
     auto run = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KC);
-        if (nb) k_sml_flux<LP><<<nb, 256, 0, st>>>(X);
+        if (!nb) return;
+        if (dd == 2) k_sml_flux<LP, 2><<<nb, 256, 0, st>>>(X);
+        else if (dd == 1) k_sml_flux<LP, 1><<<nb, 256, 0, st>>>(X);
+        else k_sml_flux<LP, 0><<<nb, 256, 0, st>>>(X);
     };
     HALO_RUN_R1(S, st, run, F_u_tend, F_u_tend);  // (u_tend at the edges of owned cells)
-    HALO_WROTE(S, X_smlS, X_Dd);
+    if (dd == 2) HALO_WROTE(S, X_smlS);
+    else HALO_WROTE(S, X_smlS, X_Dd);
     return hipGetLastError();
 }
-hipError_t launch_sml_flux(const DevState& S, hipStream_t st) { MPAS_LP_DISPATCH(S.LP, sml_flux_lp, S, st); }
+hipError_t launch_sml_flux(const DevState& S, hipStream_t st, int dd) {
+    MPAS_LP_DISPATCH(S.LP, sml_flux_lp, S, st, dd);
+}
 
 // :1581-1613 restored (Q18, MPAS vertical solver only): ru_p and ruAvg of every owned
 // edge, before the cell kernel reads ru_p.  FIRST (small_step 0): ru_p = dts tend_u and
@@ -618,7 +639,8 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
     double epssm = kEpssm;
     double resm = (1.0 - epssm) / (1.0 + epssm);
     if (mode && S.physics) return hipErrorInvalidValue;  // (srk3 never asks: reference semantics only)
-    if (ddx && S.physics) return hipErrorInvalidValue;   // (X_Dd: atm_srk3's reference semantics only)
+    if (ddx && S.physics) return hipErrorInvalidValue;   // (X_Dd / dd0: atm_srk3's reference semantics only)
+    if (ddx < 0 || ddx > 2) return hipErrorInvalidValue;
     if (S.physics) {  // Q18: the edges first
         const double rcv = kRgas / (kCp - kRgas), c2 = kCp * rcv;
         // (mdamp, option mdamp: the previous substep's damping here, coefficient coef_prev; 2: that
@@ -646,11 +668,12 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
         const int grid = ncb;
         const bool first = small_step == 0;
         if (tail) {  // (one launch: the orphan edges' blocks after the cell blocks)
-            auto go_t = [&](auto ex, auto sf, auto ac) {
+            auto go_t = [&](auto ex, auto sf, auto ac, auto d0) {
                 constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value, A = decltype(ac)::value;
+                constexpr bool D = decltype(d0)::value;
 #define MPAS_ACO(FI, TM, SM)                                                                                        \
-    k_acoustic_o<LP, E, SF, FI, TM, SM, (A && !(TM))><<<ncb + nob, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, ncb, \
-                                                                      wold, ddx, dtseps)
+    k_acoustic_o<LP, E, SF, FI, TM, SM, (A && !(TM)), D><<<ncb + nob, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, \
+                                                                         ncb, wold, D ? 0 : ddx, dtseps)
                 if (first) {
                     if constexpr (!E) {
                         if (sml == 2) {
@@ -666,25 +689,30 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
                 }
 #undef MPAS_ACO
             };
-            auto go_ts = [&](auto ex, auto ac) {
-                if (X.selfc) go_t(ex, std::true_type{}, ac);
-                else go_t(ex, std::false_type{}, ac);
+            auto go_ts = [&](auto ex, auto ac, auto d0) {
+                if (X.selfc) go_t(ex, std::true_type{}, ac, d0);
+                else go_t(ex, std::false_type{}, ac, d0);
+            };
+            auto go_td = [&](auto ex, auto ac) {
+                if (ddx == 2) go_ts(ex, ac, std::true_type{});
+                else go_ts(ex, ac, std::false_type{});
             };
             auto go_ta = [&](auto ex) {
-                if (aco) go_ts(ex, std::true_type{});
-                else go_ts(ex, std::false_type{});
+                if (aco) go_td(ex, std::true_type{});
+                else go_td(ex, std::false_type{});
             };
             if (exact) go_ta(std::true_type{});
             else go_ta(std::false_type{});
             return;
         }
-        auto go = [&](auto ex, auto sf, auto md, auto ac) {
+        auto go = [&](auto ex, auto sf, auto md, auto ac, auto d0) {
             constexpr bool E = decltype(ex)::value, SF = decltype(sf)::value, A = decltype(ac)::value;
+            constexpr bool D = decltype(d0)::value;  // (never with the MPAS forms: refused above)
             constexpr int M = decltype(md)::value;
             // (ACO: never with the MPAS forms or tmedge -- refused above)
 #define MPAS_AC(FI, MP, MM, TM, SM)                                                                                 \
-    k_acoustic<LP, E, SF, FI, MP, MM, TM, SM, (A && !(MP) && !(TM))><<<grid, 256, 0, st>>>(              \
-        X, dts, small_step, epssm, resm, coef_prev, ncb, wold, ddx, dtseps)
+    k_acoustic<LP, E, SF, FI, MP, MM, TM, SM, (A && !(MP) && !(TM)), (D && !(MP))><<<grid, 256, 0, st>>>( \
+        X, dts, small_step, epssm, resm, coef_prev, ncb, wold, D ? 0 : ddx, dtseps)
             if constexpr (M == 0) {
                 if (X.physics) {
                     if (first) MPAS_AC(true, true, 0, false, false);
@@ -710,18 +738,22 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
             }
 #undef MPAS_AC
         };
-        auto go_m = [&](auto ex, auto sf, auto ac) {
-            if (mode == 1) go(ex, sf, std::integral_constant<int, 1>{}, ac);
-            else if (mode == 2) go(ex, sf, std::integral_constant<int, 2>{}, ac);
-            else go(ex, sf, std::integral_constant<int, 0>{}, ac);
+        auto go_m = [&](auto ex, auto sf, auto ac, auto d0) {
+            if (mode == 1) go(ex, sf, std::integral_constant<int, 1>{}, ac, d0);
+            else if (mode == 2) go(ex, sf, std::integral_constant<int, 2>{}, ac, d0);
+            else go(ex, sf, std::integral_constant<int, 0>{}, ac, d0);
         };
-        auto go_s = [&](auto ex, auto ac) {
-            if (X.selfc) go_m(ex, std::true_type{}, ac);
-            else go_m(ex, std::false_type{}, ac);
+        auto go_s = [&](auto ex, auto ac, auto d0) {
+            if (X.selfc) go_m(ex, std::true_type{}, ac, d0);
+            else go_m(ex, std::false_type{}, ac, d0);
+        };
+        auto go_d = [&](auto ex, auto ac) {
+            if (ddx == 2) go_s(ex, ac, std::true_type{});
+            else go_s(ex, ac, std::false_type{});
         };
         auto go_a = [&](auto ex) {
-            if (aco) go_s(ex, std::true_type{});
-            else go_s(ex, std::false_type{});
+            if (aco) go_d(ex, std::true_type{});
+            else go_d(ex, std::false_type{});
         };
         if (exact) go_a(std::true_type{});
         else go_a(std::false_type{});
@@ -756,6 +788,7 @@ template <int LP>
 static hipError_t hf_ac_vc_lp(const DevState& S, hipStream_t st, double dts, int small_step, int exact,
                               double coef_prev, int wold, int ddx, int aco, double dts_vi) {
     if (S.physics || S.halo || small_step == 0 || S.epw != 2) return hipErrorInvalidValue;
+    if (ddx < 0 || ddx > 2) return hipErrorInvalidValue;
     const double epssm = kEpssm, resm = (1.0 - epssm) / (1.0 + epssm);
     const double dtseps = aco ? vi_dtseps(dts_vi) : 0.0;
     const int ncb = col_blocks<LP>(S, KC);
@@ -763,13 +796,18 @@ static hipError_t hf_ac_vc_lp(const DevState& S, hipStream_t st, double dts, int
     const int nv = col_blocks_n<LP, 2>(S, KV), nb2 = nv + col_blocks_n<LP, 2>(S, KC);
     if (!ncb || !nb2) return hipErrorInvalidValue;
     const int grid = nb1 + nb2;
-    auto go = [&](auto ex, auto sf, auto ac) {
-        k_hf_ac_vc<LP, decltype(ex)::value, decltype(sf)::value, 2, decltype(ac)::value><<<grid, 256, 0, st>>>(
-            S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, ddx, dtseps);
+    auto go = [&](auto ex, auto sf, auto ac, auto d0) {
+        constexpr bool D = decltype(d0)::value;
+        k_hf_ac_vc<LP, decltype(ex)::value, decltype(sf)::value, 2, decltype(ac)::value, D><<<grid, 256, 0, st>>>(
+            S, dts, small_step, epssm, resm, coef_prev, ncb, nb1, nv, wold, D ? 0 : ddx, dtseps);
+    };
+    auto go_d = [&](auto ex, auto sf, auto ac) {
+        if (ddx == 2) go(ex, sf, ac, std::true_type{});
+        else go(ex, sf, ac, std::false_type{});
     };
     auto go_a = [&](auto ex, auto sf) {
-        if (aco) go(ex, sf, std::true_type{});
-        else go(ex, sf, std::false_type{});
+        if (aco) go_d(ex, sf, std::true_type{});
+        else go_d(ex, sf, std::false_type{});
     };
     auto go_s = [&](auto ex) {
         if (S.selfc) go_a(ex, std::true_type{});

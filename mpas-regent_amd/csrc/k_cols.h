@@ -501,9 +501,12 @@ __device__ __forceinline__ void solve_e_body(const DevState& S, Blk bk) {
 // stage 0's combined hfuse launch): per cell and level k <= L the sum over the cell's edges of
 // set_smlstep's slope-flux terms, in the order every fast-path set_smlstep adds them; and X_Dd
 // = rw_save - rw for the stages' acoustic launches (the same difference they formed)
-// SETUP: beside the stage-0 setup launch that is writing rw_save = rw (every level but L): rw
-// stands in for rw_save (the same values where the acoustic step reads the difference)
-template <int LP, bool SETUP = false>
+// DD 1: beside the stage-0 setup launch that is writing rw_save = rw (every level but L), or ahead
+// of it (option smlkeep): rw stands in for rw_save (the same values where the acoustic step reads
+// the difference)
+// DD 2 (option dd0): no X_Dd at all -- the acoustic launches take the difference as the constant 0.0;
+// the kernel then reads nothing a step writes
+template <int LP, int DD = 0>
 __device__ __forceinline__ void sml_flux_body(const DevState& S, Blk bk) {
     ColMap<LP> m(S, KC, bk);
     const int L = S.L, k = m.k, c = m.ent;
@@ -540,12 +543,14 @@ __device__ __forceinline__ void sml_flux_body(const DevState& S, Blk bk) {
         sum += (zb[q] + copysign(1.0, ut) * zb3[q]) * flux;
     }
     colk(fw(S, X_smlS), c) = k <= L ? sum : 0.0;
-    double rws, rw;
-    if constexpr (SETUP) rws = rw = col_rd<LP>(fd(S, F_rw), c, k, L);
-    else col_rd2<LP>(fd(S, F_rw_save), fd(S, F_rw), c, k, L, rws, rw);
-    // (level L: 0.0 in both forms -- the SETUP form's rw stands in for rw_save, which differs there;
-    // the acoustic step reads the interfaces 1..L-1 only: ADVICE r05)
-    colk(fw(S, X_Dd), c) = k < L ? rws - rw : 0.0;
+    if constexpr (DD != 2) {
+        double rws, rw;
+        if constexpr (DD == 1) rws = rw = col_rd<LP>(fd(S, F_rw), c, k, L);
+        else col_rd2<LP>(fd(S, F_rw_save), fd(S, F_rw), c, k, L, rws, rw);
+        // (level L: 0.0 in both forms -- the DD 1 form's rw stands in for rw_save, which differs there;
+        // the acoustic step reads the interfaces 1..L-1 only: ADVICE r05)
+        colk(fw(S, X_Dd), c) = k < L ? rws - rw : 0.0;
+    }
 }
 
 // ---------------------------------------------------------------- setup + moist + vert_imp

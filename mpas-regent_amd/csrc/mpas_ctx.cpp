@@ -122,6 +122,16 @@ struct mpas_ctx {
     int accoef = 1;    // option "accoef" (atm_srk3, reference semantics): the acoustic launches form cofwr, coftz
                        // and a_tri from the columns they hold instead of loading them; stage 0's setup launch
                        // does not store the three, vert_imp takes coftz's level L from the keep tail (same bits)
+    int dd0 = 1;       // option "dd0" (atm_srk3, reference semantics): the acoustic launches take rw_save - rw as
+                       // the constant 0.0 -- the setup stores rw_save = rw where the difference is read and no
+                       // task of the step writes rw -- and load neither column, nor X_Dd (same bits for finite rw)
+    int smlkeep = 1;   // option "smlkeep" (with smlsum, undecomposed): X_smlS is formed when its inputs may have
+                       // changed (sml_valid below), ahead of the step, not in every step
+    // X_smlS (and X_Dd without dd0) hold what the flux kernel would form now.  Set by srk3_step when it has run
+    // the kernel; cleared by every public entry point but the step itself and the pure queries (guarded()):
+    // the sum's inputs -- u_tend, zb_cell, zb3_cell, edgesOnCell_sign, fzm, fzp, the mesh lists, rw -- have no
+    // writer among the step's tasks, so only a call from outside can change them
+    bool sml_valid = false;
     int fusedamp = 1;  // option "fusedamp": atm_srk3 applies each divergence damping inside the next
                        // acoustic launch (reference semantics, undecomposed; same bits)
     void* raw[X_COUNT] = {};  // the allocations behind S.f (S.f[f] = raw[f] + stagger)
@@ -535,9 +545,18 @@ void bounds_remove(mpas_ctx*) {}
 void bounds_check(mpas_ctx*) {}
 #endif
 
+// keeps_sml: the call leaves the kept flux sum (mpas_ctx::sml_valid) as it is.  The rule is "every entry
+// point clears it but ...", decided here once, not "these entry points clear it": an upload, a fill, a
+// standalone or init task, an option change or a halo call may each change an input of the sum or the form
+// of the step, and an entry point added later is then safe without anyone thinking of the flag.  The
+// exceptions pass keeps_sml: the step itself (no task of it writes an input) and the calls that write no
+// device field and no option -- download, sync, get_option, the timing calls, summarize_timestep (the
+// queries that never reach here, mpas_get_stream, mpas_field_*, mpas_halo_stats, mpas_last_error, touch
+// nothing either)
 template <class Fn>
-int guarded(mpas_ctx* c, Fn&& fn) {
+int guarded(mpas_ctx* c, Fn&& fn, bool keeps_sml = false) {
     if (!c) return MPAS_EINVAL;
+    if (!keeps_sml) c->sml_valid = false;
     try {
         fn();
         if (MPAS_BOUNDS) bounds_check(c);
@@ -909,6 +928,22 @@ void tr_rk_supported(mpas_ctx* c, const char* what) {
         throw Fail{MPAS_ENOTSUP, std::string(what) + ": not with trtile, tredge, trsu or trepw = 2"};
 }
 
+// option smlkeep: the step takes X_smlS as it stands -- an undecomposed context whose step uses the sum
+// (srk3's smls: the fast path with fusedamp, fusesml and smlsum).  Decomposed contexts form it in every
+// step: skipping the kernel there would skip its exchange of u_tend too
+bool smlkeep_active(const mpas_ctx* c) {
+    return c->smlkeep && !c->halo && c->S.physics == 0 && c->fusedamp && c->fusesml && c->smlsum && !c->exact;
+}
+// ... formed here when its inputs may have changed since the kernel last ran (mpas_ctx::sml_valid): on the
+// task stream ahead of the step and outside any capture, under the flux task's timing key.  With dd0 the
+// kernel reads nothing a step writes; without it X_Dd comes from rw alone (the setup that follows stores
+// rw_save = rw, and no task of the step writes rw), so ahead of the setup is the same computation
+void sml_ensure(mpas_ctx* c) {
+    if (!smlkeep_active(c) || c->sml_valid) return;
+    run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(c->S, c->stream, c->dd0 ? 2 : 1); });
+    c->sml_valid = true;
+}
+
 void srk3(mpas_ctx* c, double dt, int schedule) {
     // rk_timestep.rg:378-399
     const int number_of_sub_steps = 2;
@@ -967,6 +1002,13 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
     // step (X_smlS); each stage's fused set_smlstep then reads one column instead of u_tend at
     // the cell's edges and zb_cell / zb3_cell (none of them written within the step)
     const bool smls = fuse && c->fusesml && c->smlsum && !c->exact && S.physics == 0;
+    // option smlkeep (undecomposed): srk3_step formed the sum ahead of the step where its inputs may have
+    // changed since it last did (sml_ensure) -- no flux launch here, so none in a captured step
+    const bool keep = smls && smlkeep_active(c);
+    // option dd0 (reference semantics): every acoustic launch takes rw_save - rw as 0.0 (ddx 2); without it
+    // the launches of a step with smlsum read the difference from X_Dd (ddx 1), the others both columns
+    const int ddx = (c->dd0 && S.physics == 0) ? 2 : smls ? 1 : 0;
+    const int fluxf = ddx == 2 ? 2 : 1;  // (the flux body beside the setup: with X_Dd or without)
     auto stage_args = [&](int r) {
         DynTendArgs a{};
         a.rk_step = schedule == 0 ? (int)rk_sub_timestep[r] : r;  // Q4
@@ -1027,12 +1069,13 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
     // this step's setup made rho_zz_old_split from rho_zz and nothing writes either in between -- not made
     const bool norz = (c->ntu == 1 || c->ntu == 2) && S.physics == 0 && S.LP == 64 && dynamics_split == 1;
     if (c->fusesetup && S.physics == 0 && hf2) {  // + stage 0's dyn_tend A in the same launch
-        run_task(c, smls ? "hfuse[setup+dyn_A+sml_flux]" : "hfuse[setup+dyn_A]", [&] {
-            return launch_hf_setup_dyn_A(S, st, stage_args(0), rk_sub_timestep[0], fcopy ? 0 : 1, smls ? 1 : 0);
+        const bool fl = smls && !keep;
+        run_task(c, fl ? "hfuse[setup+dyn_A+sml_flux]" : "hfuse[setup+dyn_A]", [&] {
+            return launch_hf_setup_dyn_A(S, st, stage_args(0), rk_sub_timestep[0], fcopy ? 0 : 1, fl ? fluxf : 0);
         });
         dts_vi = rk_sub_timestep[0];
         a_done = true;
-        flux_done = smls;
+        flux_done = fl;
     } else if (c->fusesetup) {  // :404-417 as one column-local launch (same values; MPAS forms under physics)
         // (option ntu: stage 0's vert_imp leaves b_tri / c_tri unstored -- no task reads them and stage 1's
         // vert_imp, which always runs, rewrites both; "-bc")
@@ -1047,8 +1090,8 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[0]); });
         dts_vi = rk_sub_timestep[0];
     }
-    if (smls && !flux_done)
-        run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st); });
+    if (smls && !keep && !flux_done)
+        run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st, ddx == 2 ? 2 : 0); });
     for (int rk_step = 0; rk_step < 3; rk_step++) {  // :426-477
         if (rk_step == 1 && !vi_done) {
             run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[rk_step]); });
@@ -1088,8 +1131,8 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                 const int wold = ((done_acoustic + 1 == n_acoustic) ? 1 : 0) | nst;
                 if (hf2 && rk_step < 2 && mode == 2 && small_step > 0 && small_step == n_small - 1) {
                     run_task(c, nst ? "hfuse[acoustic-st+solve_vc]" : "hfuse[acoustic+solve_vc]", [&] {
-                        return launch_hf_acoustic_solve_vc(S, st, dts, small_step, c->exact, coef_prev, wold, smls ? 1 : 0,
-                                                           aco, dts_vi);
+                        return launch_hf_acoustic_solve_vc(S, st, dts, small_step, c->exact, coef_prev, wold, ddx, aco,
+                                                           dts_vi);
                     });
                     vc_done = true;
                 } else {
@@ -1099,7 +1142,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                                                : std::string(acoustic_name(small_step, pending, sm, !(wold & 1)));
                     run_task(c, an.c_str(),
                              [&] { return launch_acoustic(S, st, dts, small_step, c->exact, mode, coef_prev, tme, sm, wold,
-                                                          smls ? 1 : 0, 0, 0, aco, dts_vi); });
+                                                          ddx, 0, 0, aco, dts_vi); });
                 }
                 if (mode == 2) fb.swap_rup();
                 fb.swap_dv();  // this substep's div is read next from X_dvB
@@ -1128,7 +1171,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
             // ("-ru": option mru, this first substep's ru_p / ruAvg were stored by the stage's dyn_tend)
             const std::string anw = (small_step == 0 && ru_done) ? an1.substr(0, an1.size() - 1) + "-ru]" : an1;
             run_task(c, anw.c_str(), [&] {
-                return launch_acoustic(S, st, dts, small_step, c->exact, 0, cprev, tme, 0, nww ? 3 : 1, 0, mdp,
+                return launch_acoustic(S, st, dts, small_step, c->exact, 0, cprev, tme, 0, nww ? 3 : 1, ddx, mdp,
                                        (small_step == 0 && ru_done) ? 1 : 0, aco, dts_vi);
             });
             if (!md_fold)
@@ -1244,6 +1287,7 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
     Halo* h = c->halo.get();
     const bool halo_graph = h && !h->loop && (h->stub ? c->graph_halo != 0 : (h->rccl && c->graph_halo == 1)) &&
                             !c->graph_refused;
+    sml_ensure(c);
     if (!c->graph_on || c->timing || (h && !halo_graph)) {
         srk3(c, dt, schedule);
         return;
@@ -1469,7 +1513,7 @@ int mpas_sync(mpas_ctx* c) {
     return guarded(c, [&] {
         hipcheck(hipSetDevice(c->device), "hipSetDevice");
         hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    });
+    }, true);
 }
 
 int mpas_get_stream(mpas_ctx* c, void** stream) {
@@ -1492,6 +1536,13 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         else if (name && std::strcmp(name, "accoef") == 0) {
             if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "accoef must be 0 or 1"};
             c->accoef = (int)value;
+        }
+        else if (name && std::strcmp(name, "dd0") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "dd0 must be 0 or 1"};
+            c->dd0 = (int)value;
+        } else if (name && std::strcmp(name, "smlkeep") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "smlkeep must be 0 or 1"};
+            c->smlkeep = (int)value;
         }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
@@ -1665,6 +1716,8 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "ntu") == 0) *value = c->ntu;
         else if (name && std::strcmp(name, "mdamp") == 0) *value = c->mdamp;
         else if (name && std::strcmp(name, "accoef") == 0) *value = c->accoef;
+        else if (name && std::strcmp(name, "dd0") == 0) *value = c->dd0;
+        else if (name && std::strcmp(name, "smlkeep") == 0) *value = c->smlkeep;
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;
         else if (name && std::strcmp(name, "vdyn") == 0) *value = c->vdyn;
@@ -1715,7 +1768,7 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
             }
             *value = c->S.selfc;
         } else throw Fail{MPAS_EINVAL, std::string("unknown option ") + (name ? name : "(null)")};
-    });
+    }, true);
 }
 
 int mpas_upload(mpas_ctx* c, int f, const void* host, int64_t se, int64_t sl, int64_t sc) {
@@ -1872,7 +1925,7 @@ int mpas_download(mpas_ctx* c, int f, void* host, int64_t se, int64_t sl, int64_
         if (dview)  // the staged image back into the device view (the bytes between its
                     // elements came from it, so they are unchanged)
             hipcheck(hipMemcpy(dview, staged.data(), staged.size(), hipMemcpyHostToDevice), "hipMemcpy H2D (view)");
-    });
+    }, true);
 }
 
 int mpas_fill_synthetic(mpas_ctx* c, uint64_t seed) {
@@ -1993,6 +2046,7 @@ int mpas_halo_loopback(mpas_ctx** ctxs, int n) {
     if (!ctxs || n < 1) return MPAS_EINVAL;
     for (int i = 0; i < n; i++)
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) return MPAS_EINVAL;
+    for (int i = 0; i < n; i++) ctxs[i]->sml_valid = false;
     return guarded(ctxs[0], [&] {
         hipcheck(hipSetDevice(ctxs[0]->device), "hipSetDevice");
         auto g = std::make_shared<LoopGroup>();
@@ -2215,31 +2269,33 @@ int mpas_summarize_timestep(mpas_ctx* c, int detailed, int global_vel, int globa
                 for (int i = 27; i < 31; i++) h[i] = 0.0;
         }
         std::memcpy(out, h, sizeof h);
-    });
+    }, true);
 }
 
 int mpas_atm_srk3(mpas_ctx* c, double dt, int schedule) {
-    return guarded(c, [&] {
+    const int rc = guarded(c, [&] {
         hipcheck(hipSetDevice(c->device), "hipSetDevice");
         if (c->transport == 2) tr_rk_supported(c, "atm_srk3 with transport = 2");  // (never inside a capture)
         srk3_step(c, dt, schedule);
-    });
+    }, true);
+    if (c && rc != MPAS_OK) c->sml_valid = false;  // (a failed step promises nothing)
+    return rc;
 }
 int mpas_atm_timestep(mpas_ctx* c, double dt) { return mpas_atm_srk3(c, dt, 0); }
 
 int mpas_timing_enable(mpas_ctx* c, int on) {
-    return guarded(c, [&] { c->timing = on != 0; });
+    return guarded(c, [&] { c->timing = on != 0; }, true);
 }
 int mpas_timing_reset(mpas_ctx* c) {
     return guarded(c, [&] {
         harvest(c);
         for (auto& x : c->task_calls) x = 0;
         for (auto& x : c->task_ms) x = 0.0;
-    });
+    }, true);
 }
 int mpas_timing_count(mpas_ctx* c) {
     if (!c) return MPAS_EINVAL;
-    int rc = guarded(c, [&] { harvest(c); });
+    int rc = guarded(c, [&] { harvest(c); }, true);
     return rc != MPAS_OK ? rc : (int)c->task_names.size();
 }
 int mpas_timing_get(mpas_ctx* c, int idx, const char** name, int64_t* calls, double* total_ms) {
@@ -2249,7 +2305,7 @@ int mpas_timing_get(mpas_ctx* c, int idx, const char** name, int64_t* calls, dou
         if (name) *name = c->task_names[idx].c_str();
         if (calls) *calls = c->task_calls[idx];
         if (total_ms) *total_ms = c->task_ms[idx];
-    });
+    }, true);
 }
 
 }  // extern "C"

@@ -97,7 +97,7 @@ enum FieldId {
                 // written by any task of the step) for the stages' fused set_smlstep      C3
     X_Dd,       // rw_save - rw per cell and level, formed with X_smlS once per step (neither is
                 // written within a step in the reference semantics): the acoustic step's only use
-                // of the two columns                                                      C3
+                // of the two columns (option dd0 = 0; with dd0 it is not formed or read)   C3
     // monotonic scalar transport (k_transport.hip), one column per (entity, scalar)
     X_Ah,       // antidiffusive edge flux                                      E3 x 8
     X_Rp,       // R+ (fraction of the incoming antidiffusive flux allowed)     C3V x 8
@@ -255,7 +255,7 @@ hipError_t launch_hf_acoustic_solve_vc(const DevState& S, hipStream_t st, double
                                        double coef_prev, int wold = 1, int ddx = 0, int aco = 0, double dts_vi = 0.0);
 hipError_t launch_hf_solve_e_dyn_A(const DevState& S, hipStream_t st, const DynTendArgs& next, int vi, double dts_vi);
 // ... and stage 0's setup + moist + vert_imp launch (fusesetup) beside stage 0's dyn_tend A
-// flux: also set_smlstep's flux sum of the step (X_smlS; option smlsum)
+// flux: also set_smlstep's flux sum of the step (X_smlS; option smlsum) -- 1 with X_Dd, 2 without (option dd0)
 hipError_t launch_hf_setup_dyn_A(const DevState& S, hipStream_t st, const DynTendArgs& stage0, double dts, int edges,
                                  int flux = 0);
 hipError_t launch_dyn_tend(const DevState& S, hipStream_t st, const DynTendArgs& a);
@@ -270,7 +270,8 @@ hipError_t launch_set_smlstep(const DevState& S, hipStream_t st, int exact);
 // 1 from its slope fluxes, 2 (exact = 0) from X_smlS, the step's launch_sml_flux
 // wold 0 (mode 1 / 2 only): rtheta_pp_old not stored -- atm_srk3's fused damping reads the div
 // this launch stores instead, so only the step's last substep leaves rtheta_pp_old
-// ddx: rw_save - rw from X_Dd (atm_srk3 with option smlsum: launch_sml_flux formed it this step)
+// ddx: 1 rw_save - rw from X_Dd (atm_srk3 with option smlsum: launch_sml_flux formed it); 2 the constant
+// 0.0 (atm_srk3 with option dd0: the setup stored rw_save = rw and no task of the step writes rw)
 hipError_t launch_acoustic(const DevState& S, hipStream_t st, double dts, int small_step, int exact, int mode = 0,
                            double coef_prev = 0.0, int tme = 0, int sml = 0, int wold = 1, int ddx = 0,
                            int mdamp = 0,   // (mdamp: the MPAS forms, the previous substep's damping folded in)
@@ -280,8 +281,9 @@ hipError_t launch_acoustic(const DevState& S, hipStream_t st, double dts, int sm
                            // that formed the live coefficient set (not this launch's dts)
                            int aco = 0, double dts_vi = 0.0);
 // X_smlS = the sum of set_smlstep's slope-flux terms per cell and level (atm_srk3 fast path,
-// once per step: u_tend / zb_cell / zb3_cell are not written within a step)
-hipError_t launch_sml_flux(const DevState& S, hipStream_t st);
+// u_tend / zb_cell / zb3_cell are not written by any task of a step); dd 0: also X_Dd = rw_save - rw
+// (after the step's setup), 1: the same from rw alone (ahead of the setup), 2: no X_Dd (option dd0)
+hipError_t launch_sml_flux(const DevState& S, hipStream_t st, int dd = 0);
 // old_zero: only from srk3, right after a stage's first acoustic substep (k_div_damp OLD0)
 hipError_t launch_div_damping(const DevState& S, hipStream_t st, double dts, int old_zero = 0);
 // the damping from the div buffer X_dvB (fusedamp: the step's last substep), ru_p in place
