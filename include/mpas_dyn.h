@@ -310,6 +310,30 @@ int mpas_atm_advance_scalars(mpas_ctx* ctx, double dt);
  *       last stage of the RK3 scalar transport.  Bit-identical to mpas_atm_advance_scalars_mono
  *       when scalars equals scalars_old on entry.  MPAS_ENOTSUP as above. */
 int mpas_atm_advance_scalars_mono_rk(mpas_ctx* ctx, double dt);
+/* The Held-Suarez (1994) forcing: Newtonian relaxation of temperature to a prescribed radiative
+ *       equilibrium and Rayleigh friction below sigma_b -- the two physics tendencies the MPAS forms
+ *       of dyn_tend read ("physics" = 2).  No reference entry point (SURVEY scopes the reference's
+ *       physics out, and it is stubs).  Reads the state as found.  With sigma_b = 0.7, k_f = 1/86400,
+ *       k_a = 1/(40 86400), k_s = 1/(4 86400) (1/s), dTy = 60 K, dthz = 10 K, floor = 200 K,
+ *       p0 = 1e5 Pa, g = 9.80616 and c2 = cos(latCell)^2 (glibc cos on the host, at upload), per
+ *       owned cell c and level k < nVertLevels, rq(k) = rho_zz(k) (1 + qtot(k)):
+ *         p     = pressure_base + pressure_p
+ *         ps    = 0.5 (1 / rdzw(0)) g (1.25 rq(0) - 0.25 rq(1)) + pressure_p(0) + pressure_base(0)
+ *                 (atm_compute_output_diagnostics' surface pressure; level 1 as found at nVertLevels = 1)
+ *         sigma = p / ps;  w = max(0, (sigma - sigma_b) / (1 - sigma_b))
+ *         kv    = k_f w;   kT = k_a + (k_s - k_a) w c2 c2
+ *         theq  = max(floor / exner, 315 - dTy (1 - c2) - dthz log(p / p0) c2)
+ *         tend_rtheta_physics = -kT rho_zz (theta_m - theq)
+ *       and per owned edge e of cells c1, c2 = cellsOnEdge(e, 0:1):
+ *         tend_ru_physics = -(0.5 (kv(c1,k) + kv(c2,k))) ru(e,k)
+ *       Dry: theta_m stands for theta, the scalars stay passive.  Writes those two fields on levels
+ *       0..nVertLevels-1 and no other field; level nVertLevels and the zero slot keep their values.
+ *       Statement order: tests/forcing_ref.py (bit for bit but for log).  Decomposed contexts
+ *       exchange the kv scratch on their ghost cells like every gathered field.
+ *       Option "forcing" = 1 (needs "physics" = 2, else MPAS_EINVAL; a value other than 0 or 1:
+ *       MPAS_EINVAL; default 0; reset to 0 when "physics" leaves 2) makes mpas_atm_srk3 run this
+ *       task once per step, ahead of stage 0's setup: the tendencies are held over the three stages. */
+int mpas_atm_held_suarez_forcing(mpas_ctx* ctx);
 /* rk_timestep.rg:29 summarize_timestep(cr, er, config_print_detailed_minmax_vel,
  *       config_print_global_minmax_vel, config_print_global_minmax_sca): the values the
  *       reference prints, into out[31] (host memory; the call synchronises):

@@ -279,7 +279,7 @@ static hipError_t recover_lp(const DevState& S, hipStream_t st, int ns, int rk_s
     a.invNs = 1 / (double)ns;
     a.dt = dt;
     a.rgas = kRgas;
-    a.rgas_p0 = kRgas / 100000;
+    a.rgas_p0 = kRgas / kP0;
     a.rcv = kRgas / (kCp - kRgas);
     a.rk_step = rk_step;
     a.coef_divdamp = damp ? divdamp_coef(damp_dts) : 0.0;
@@ -449,7 +449,7 @@ static hipError_t icd_lp(const DevState& S, hipStream_t st) {
     HALO_WROTE(S, F_ru);
     auto kc = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KC);
-        if (nb) k_icd_cells<LP><<<nb, 256, 0, st>>>(X, kRgas / 100000, kRgas, kRgas / (kCp - kRgas));
+        if (nb) k_icd_cells<LP><<<nb, 256, 0, st>>>(X, kRgas / kP0, kRgas, kRgas / (kCp - kRgas));
     };
     HALO_RUN(S, st, kc, F_ru);
     HALO_WROTE(S, F_rw, F_rho_p, F_rtheta_base, F_rtheta_p, F_exner, F_exner_base, F_pressure_p, F_pressure_base);

@@ -62,6 +62,7 @@ const FieldInfo kFields[X_COUNT] = {
     {"Rp", K_C3V, 8, D_M, 0, 0},
     {"Rm", K_C3V, 8, D_M, 0, 0},
     {"su", K_C3V, 8, D_M, 0, 0},
+    {"hskv", K_C3, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -91,6 +92,10 @@ struct mpas_ctx {
     // option "transport": atm_srk3 runs the scalar transport (physics >= 1) -- 1 the monotonic task once
     // over dt, 2 MPAS's RK3 form: two unlimited stages over dt/3 and dt/2, then the monotonic task over dt
     int transport = 0;
+    // option "forcing" (the MPAS dynamics, physics = 2): 1 -- atm_srk3 runs the Held-Suarez forcing task once per
+    // step, ahead of stage 0's setup; its two tendencies are held over the three stages (as MPAS-A holds its
+    // physics tendencies).  0: the step never writes them
+    int forcing = 0;
     int self_on = 1;   // option "self": allow the SELF gathers when the mesh permits
     int self_ok = 0;   // k_prepare's verdict on the uploaded mesh
     int overlap = 1;   // option "overlap": halo exchanges beside interior compute
@@ -275,7 +280,9 @@ const int kKeepL[] = {
     // substep_finish
     F_wwAvg_split, F_ruAvg_split,
     // mpas_reconstruct_2d
-    F_uReconstructX, F_uReconstructY, F_uReconstructZ, F_uReconstructZonal, F_uReconstructMeridional};
+    F_uReconstructX, F_uReconstructY, F_uReconstructZ, F_uReconstructZonal, F_uReconstructMeridional,
+    // the Held-Suarez forcing
+    F_tend_rtheta_physics, F_tend_ru_physics};
 const int kKeep0[] = {F_cofwr, F_cofwz, F_a_tri, F_b_tri, F_c_tri, F_alpha_tri, F_cqw, F_rw};
 int keep_kind(int f) { return kFields[f].kind == K_C3 ? 0 : kFields[f].kind == K_E3 ? 1 : 2; }  // KC / KE / KV
 
@@ -1068,6 +1075,9 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
     // option ntu (reference semantics): the substep finish's rho_zz = rho_zz_old_split is the identity --
     // this step's setup made rho_zz_old_split from rho_zz and nothing writes either in between -- not made
     const bool norz = (c->ntu == 1 || c->ntu == 2) && S.physics == 0 && S.LP == 64 && dynamics_split == 1;
+    // option forcing: the physics tendencies of the step, from the state the step starts from; every stage's
+    // dyn_tend (the MPAS forms) reads them, no task of the step writes them
+    if (c->forcing) run_task(c, "atm_held_suarez_forcing", [&] { return launch_held_suarez_forcing(S, st); });
     if (c->fusesetup && S.physics == 0 && hf2) {  // + stage 0's dyn_tend A in the same launch
         const bool fl = smls && !keep;
         run_task(c, fl ? "hfuse[setup+dyn_A+sml_flux]" : "hfuse[setup+dyn_A]", [&] {
@@ -1576,6 +1586,7 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
                 throw Fail{MPAS_EINVAL, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)"};
             c->S.physics = (int)value;
             if (!value) c->transport = 0;
+            if (value != 2) c->forcing = 0;
             c->ett_dirty = true;
         } else if (name && std::strcmp(name, "trorder_e") == 0) {
             if (value < 0 || value > (1 << 20)) throw Fail{MPAS_EINVAL, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"};
@@ -1636,6 +1647,11 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
             if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "transport must be 0, 1 (one monotonic update) or 2 (RK3)"};
             if (value && !c->S.physics) throw Fail{MPAS_EINVAL, "transport needs physics = 1 (it reads the recovered ruAvg, wwAvg, rho_zz)"};
             c->transport = (int)value;
+        } else if (name && std::strcmp(name, "forcing") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "forcing must be 0 or 1 (Held-Suarez)"};
+            if (value && c->S.physics != 2)
+                throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
+            c->forcing = (int)value;
         } else if (name && std::strcmp(name, "overlap") == 0) {
             c->overlap = value ? 1 : 0;
             if (c->halo) c->halo->overlap = c->overlap;
@@ -1663,6 +1679,7 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "vcmix") == 0) *value = c->S.vcmix;
         else if (name && std::strcmp(name, "physics") == 0) *value = c->S.physics;
         else if (name && std::strcmp(name, "transport") == 0) *value = c->transport;
+        else if (name && std::strcmp(name, "forcing") == 0) *value = c->forcing;
         else if (name && std::strcmp(name, "trorder") == 0) *value = c->S.tro;
         else if (name && std::strcmp(name, "trsu") == 0) *value = c->S.trsu;
         else if (name && std::strcmp(name, "trepw") == 0) *value = c->S.trepw;
@@ -2247,6 +2264,9 @@ int mpas_atm_advance_scalars_mono_rk(mpas_ctx* c, double dt) {
             return launch_advance_scalars_mono_rk(c->S, c->stream, dt);
         });
     });
+}
+int mpas_atm_held_suarez_forcing(mpas_ctx* c) {
+    MPAS_TASK("atm_held_suarez_forcing", launch_held_suarez_forcing(c->S, c->stream));
 }
 int mpas_atm_compute_output_diagnostics(mpas_ctx* c) {
     MPAS_TASK("atm_compute_output_diagnostics", launch_output_diagnostics(c->S, c->stream));

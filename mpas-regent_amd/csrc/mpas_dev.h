@@ -103,6 +103,9 @@ enum FieldId {
     X_Rp,       // R+ (fraction of the incoming antidiffusive flux allowed)     C3V x 8
     X_Rm,       // R- (outgoing)                                                C3V x 8
     X_su,       // the upwind update                                            C3V x 8
+    // Held-Suarez forcing (k_forcing.hip)
+    X_hskv,     // the Rayleigh friction rate kv per cell and level (zeros from level L up): formed by
+                // the task's cell kernel, gathered at the two cells of each edge by its edge kernel   C3
     X_COUNT
 };
 
@@ -182,6 +185,15 @@ constexpr int kRayleighLevels = 6;
 constexpr double kRayleighDays = 5.0;
 constexpr double kSecondsPerDay = 86400.0;
 constexpr double kSphereRadius = 6371229.0;
+constexpr double kP0 = 100000.0;  // the reference pressure: exner's rgas / p0 (k_diag.hip), the forcing's log(p / p0)
+// Held-Suarez (1994) forcing (k_forcing.hip; identical to tests/forcing_ref.py)
+constexpr double kHsSigmaB = 0.7;                              // top of the friction layer
+constexpr double kHsKf = 1.0 / kSecondsPerDay;                 // friction rate at the surface, 1/s
+constexpr double kHsKa = 1.0 / (40.0 * kSecondsPerDay);        // thermal relaxation rate aloft
+constexpr double kHsKs = 1.0 / (4.0 * kSecondsPerDay);         // ... at the surface on the equator
+constexpr double kHsDeltaTy = 60.0;                            // equator-to-pole temperature difference, K
+constexpr double kHsDeltaThz = 10.0;                           // vertical potential temperature difference, K
+constexpr double kHsFloor = 200.0;                             // the stratosphere's temperature, K
 
 // dyn_tend configuration (the Regent task's scalar arguments, dynamics_tasks.rg:818-823)
 struct DynTendArgs {
@@ -321,6 +333,8 @@ hipError_t launch_advance_scalars_mono(const DevState& S, hipStream_t st, double
 // (the default transport kernels only)
 hipError_t launch_advance_scalars(const DevState& S, hipStream_t st, double dt);
 hipError_t launch_advance_scalars_mono_rk(const DevState& S, hipStream_t st, double dt);
+// the Held-Suarez forcing (k_forcing.hip; the MPAS dynamics): tend_rtheta_physics, tend_ru_physics
+hipError_t launch_held_suarez_forcing(const DevState& S, hipStream_t st);
 hipError_t launch_damping_coefs(const DevState& S, hipStream_t st, double zd, double xnutr);
 hipError_t launch_compute_signs(const DevState& S, hipStream_t st);
 // strided device view <-> LP-padded 3-D field (elem 8: fp64, 1: uint8 masks)

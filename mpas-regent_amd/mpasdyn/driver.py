@@ -5,6 +5,7 @@ state -> atm_core_init's one-time precompute -> time steps -> atm_compute_output
     python -m mpasdyn.driver [--grid x1.N.grid.nc] [--levels 26] [--steps 10] [--dt 720]
                              [--schedule 1] [--physics {0,1,2}] [--transport] [--day]
                              [--transport-scheme {single,rk3}] [--out timestep_output.nc]
+                             [--forcing held-suarez] [--days N]
 
 Without --grid the reference's own x1.2562 mesh (tests/golden fixture) is used.  The mesh
 is taken in mpas-mode (0-based) ids, the ids the JW state (mpasdyn/jw.py) is defined on.
@@ -17,7 +18,11 @@ diagnostics (solve_diagnostics at rk_step -1 and the cell-centre winds, atm_core
 and reports the surface pressure (min/max/mean, hPa) and the global dry mass after the
 last step; `--day` sets the steps to one simulated day (86400 / dt).  `--transport` advects the
 8 scalars: `--transport-scheme single` (default) with one monotonic update over dt, `rk3` with
-MPAS-A's three-stage RK3 (option "transport" = 2, include/mpas_dyn.h)."""
+MPAS-A's three-stage RK3 (option "transport" = 2, include/mpas_dyn.h).  `--forcing held-suarez`
+(implies `--physics 2`) runs the Held-Suarez forcing in every step (option "forcing" = 1): Newtonian
+relaxation of temperature and boundary-layer friction, the long forced integration of a dry core;
+the final report then also gives the global mean temperature of the lowest level and the largest
+|uReconstructZonal|.  `--days N` sets the steps to N simulated days."""
 import argparse
 import os
 import sys
@@ -26,8 +31,9 @@ import numpy as np
 
 
 def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=False, out=None, device=0,
-        log=print):
-    """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport"""
+        log=print, forcing=None):
+    """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport;
+    forcing: None or "held-suarez" (the MPAS dynamics: physics becomes 2)"""
     from . import build_state as bs
     from . import jw, lib
     from . import mesh as M
@@ -36,13 +42,17 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         m = M.zero_based(m)
     st = bs.build_state(m, L, "physical", vertical=False)
     jw.init_atm_case_jw(m, st)
-    physics = int(physics) if physics else (1 if transport else 0)
+    if forcing not in (None, "held-suarez"):
+        raise ValueError(f"unknown forcing {forcing!r}")
+    physics = 2 if forcing else int(physics) if physics else (1 if transport else 0)
     nC = m.nCells
     vol = 1.0 / (st["invAreaCell"][:nC, 0][:, None] * st["rdzw"][:L][None, :])
     mass0 = float(np.sum(st["rho_zz"][:nC, :L] * vol))
     with lib.Context(m.nCells, m.nEdges, m.nVertices, L, device=device) as ctx:
         ctx.set_option("physics", physics)
         ctx.set_option("transport", int(transport))
+        if forcing:
+            ctx.set_option("forcing", 1)
         ctx.upload(st)
         if physics == 2:  # MPAS-A's atm_core_init diagnostics of the initial state
             T.atm_compute_solve_diagnostics(ctx, False, -1)
@@ -60,6 +70,12 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         mass = float(np.sum(st["rho_zz"][:nC, :L] * vol))
         log(f"after {steps} steps ({steps * dt / 3600.0:g} h): surface pressure [{sp.min():.4f}, {sp.max():.4f}] "
             f"mean {sp.mean():.6f} hPa; dry mass change {mass / mass0 - 1.0:.3e}")
+    if forcing:  # (dry: theta_m is theta, T = theta exner; the mean weighted by the cell areas)
+        area = 1.0 / st["invAreaCell"][:nC, 0]
+        t0 = st["theta_m"][:nC, 0] * st["exner"][:nC, 0]
+        uz = np.abs(st["uReconstructZonal"][:nC, :L])
+        log(f"{forcing}: lowest-level temperature mean {float(np.sum(t0 * area) / np.sum(area)):.4f} K; "
+            f"max |uReconstructZonal| {float(uz.max()):.4f} m/s")
     if out:
         from .meshio import write_output_plotting
         write_output_plotting(out, m, st)
@@ -79,6 +95,9 @@ def main(argv=None):
     ap.add_argument("--transport", action="store_true")
     ap.add_argument("--transport-scheme", choices=["single", "rk3"], default="single",
                     help="with --transport: one monotonic update over dt, or MPAS-A's RK3 (two unlimited stages first)")
+    ap.add_argument("--forcing", choices=["held-suarez"], default=None,
+                    help="held-suarez: Newtonian relaxation and boundary-layer friction in every step (implies --physics 2)")
+    ap.add_argument("--days", type=float, default=None, help="N simulated days: steps = N 86400 / dt")
     ap.add_argument("--out", default="timestep_output.nc")
     a = ap.parse_args(argv)
     from . import mesh as M
@@ -88,8 +107,10 @@ def main(argv=None):
     else:
         m = M.load_x1_2562()
     steps = int(round(86400.0 / a.dt)) if a.day else a.steps
+    if a.days is not None:
+        steps = int(round(a.days * 86400.0 / a.dt))
     transport = (2 if a.transport_scheme == "rk3" else 1) if a.transport else 0
-    run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out)
+    run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out, forcing=a.forcing)
     return 0
 
 

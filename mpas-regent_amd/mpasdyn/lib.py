@@ -25,7 +25,7 @@ EXPORTS = [
     "mpas_atm_rk_dynamics_substep_finish", "mpas_atm_srk3", "mpas_atm_timestep",
     "mpas_atm_recover_large_step_variables_work", "mpas_reconstruct_2d", "mpas_summarize_timestep",
     "mpas_atm_compute_output_diagnostics", "mpas_atm_advance_scalars_mono",
-    "mpas_atm_advance_scalars", "mpas_atm_advance_scalars_mono_rk",
+    "mpas_atm_advance_scalars", "mpas_atm_advance_scalars_mono_rk", "mpas_atm_held_suarez_forcing",
     "mpas_atm_compute_damping_coefs", "mpas_atm_init_coupled_diagnostics", "mpas_atm_core_init",
     "mpas_halo_ring1", "mpas_atm_compute_signs", "mpas_atm_adv_coef_compression", "mpas_atm_couple_coef_3rd_order",
     "mpas_atm_compute_mesh_scaling",
@@ -91,6 +91,7 @@ def load():
         "mpas_atm_advance_scalars_mono": (i32, [vp, dbl]),
         "mpas_atm_advance_scalars": (i32, [vp, dbl]),
         "mpas_atm_advance_scalars_mono_rk": (i32, [vp, dbl]),
+        "mpas_atm_held_suarez_forcing": (i32, [vp]),
         "mpas_atm_compute_damping_coefs": (i32, [vp, dbl, dbl]),
         "mpas_atm_init_coupled_diagnostics": (i32, [vp]),
         "mpas_atm_core_init": (i32, [vp]),

@@ -255,6 +255,12 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
     if task == "mpas_reconstruct_2d":
         return (["u", "coeffs_reconstruct", "edgesOnCell", "nEdgesOnCell", "lat", "lon"],
                 ["uReconstructX", "uReconstructY", "uReconstructZ", "uReconstructZonal", "uReconstructMeridional"])
+    if task == "atm_held_suarez_forcing":  # k_forcing.hip (option forcing; no reference task)
+        # cell kernel: six C3 columns read (p = pressure_base + pressure_p; rho_zz and qtot, also for ps;
+        # theta_m; exner), one written; edge kernel: ru read, one E3 column written.  The kv scratch the
+        # cell kernel stores and the edge kernel gathers (X_hskv) takes no credit, as every scratch
+        return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "lat", "ru", "cellsOnEdge"],
+                ["tend_rtheta_physics", "tend_ru_physics"])
     raise KeyError(task)
 
 

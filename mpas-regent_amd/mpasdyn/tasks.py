@@ -151,6 +151,12 @@ def atm_advance_scalars_mono_rk(ctx, dt):
     ctx._check(ctx.lib.mpas_atm_advance_scalars_mono_rk(ctx.h, float(dt)), "atm_advance_scalars_mono_rk")
 
 
+def atm_held_suarez_forcing(ctx):
+    """The Held-Suarez forcing: tend_rtheta_physics and tend_ru_physics from the state as found (no
+    reference task; include/mpas_dyn.h, restated by tests/forcing_ref.py)"""
+    ctx._check(ctx.lib.mpas_atm_held_suarez_forcing(ctx.h), "atm_held_suarez_forcing")
+
+
 def summarize_timestep(ctx, config_print_detailed_minmax_vel=False, config_print_global_minmax_vel=False,
                        config_print_global_minmax_sca=False):
     """rk_timestep.rg:29; returns the 31 values the reference prints (layout: include/mpas_dyn.h)"""
