@@ -161,7 +161,18 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * mpas_get_option, mpas_get_stream, mpas_timing_*, mpas_field_*, mpas_halo_stats, mpas_last_error,
  * mpas_summarize_timestep): a changed u_tend / zb_cell / zb3_cell counts at the very next step.
  * Device memory of a context written behind this interface is not seen.  A value other than 0 or
- * 1: MPAS_EINVAL.  "trepw" = 2 (speed only; measured within 2 %, default 1): two
+ * 1: MPAS_EINVAL.  "stepkeep" = 1 (default; speed only; where "smlkeep" applies, with "ntu" = 1, "defer4",
+ * "fusesetup", "fusecopy" and "accoef" on, "hfuse", "tmedge", "etile", the transport and the forcing off,
+ * stage 0 at rk_step 0 and stages 1, 2 at rk_step > 0): no task of the reference-semantics step writes u,
+ * ru, rw, rho_zz, theta_m, rho_p, rtheta_p, h, zz, exner or the base fields, so a step that follows a full
+ * step with the same dt and schedule, and no call in between but those "smlkeep" lists, runs no
+ * solve_diagnostics launch and stores none of the setup's copies of those fields nor qtot / cqw: they hold
+ * what it would store.  "stepkeep" = 2 also drops stage 0's dyn_tend from the third such step on (its w is
+ * restored from a copy; stage 2 forms tend_u, v and w alone): every field bit-identical either way, but the
+ * per-task timing of such a step has no rk_step 0 dyn_tend row.  0: every launch in every step.  A non-finite
+ * value in one of those fields then no longer re-enters each step.  Any other value: MPAS_EINVAL.  Read-only
+ * "stepkeep_gen": the steps completed since the last call that could have changed a field or the form of
+ * the step (0, 1, or 2 for two and more).  "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of
  * compact cell tiles in LDS and no edge scratch, when every cell has at most 6 edges with

@@ -560,11 +560,35 @@ __device__ __forceinline__ void sml_flux_body(const DevState& S, Blk bk) {
 // MPASV (physics >= 1): vert_imp's MPAS form (vi_column); MD (physics = 2): also setup's
 // theta_m_save = theta_m and moist's edge loop cqu = 1 / (1 + qtotal) (k_moist_edges), by the
 // edge blocks, from the qtot this launch zeroes everywhere
-template <int LP, bool MPASV = false, bool MD = false>
+// KEPT (atm_srk3 option stepkeep, reference semantics, a step after a full one with nothing written from
+// outside in between): rw, rtheta_p, rho_p, theta_m and rho_zz have no writer among the step's tasks, so
+// rw_save, rtheta_p_save, rho_p_save, theta_m_2, rho_zz_2, rho_zz_old_split, qtot and cqw hold what this
+// launch would store -- none of them is stored, and rw, rho_p and rho_zz are not loaded.  Left: w_2 = w (level
+// L of w evolves) and vert_imp (gamma_tri's recurrence over calls, Q17), with qtot / cqw as the constants
+// moist writes; the nine remaining loads paired again with no dead half.  Cell blocks only, copies = 6
+template <int LP, bool MPASV = false, bool MD = false, bool KEPT = false>
 __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double dtseps, double rcv, double c2, Blk bk,
                                               int copies = 1) {
+    static_assert(!KEPT || (!MPASV && !MD), "the kept setup: reference semantics");
     const int L = S.L, k = (int)(threadIdx.x % LP);
     int blk = bk.b;
+    if constexpr (KEPT) {
+        const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
+        if (c >= S.nCO) return;
+        double rtp, w, tm, zz, exner, rb, rtb, exb;
+        gather2<LP>(fd(S, F_rtheta_p), c, fd(S, F_w), c, k, rtp, w);
+        gather2<LP>(fd(S, F_theta_m), c, fd(S, F_zz), c, k, tm, zz);
+        gather2<LP>(fd(S, F_exner), c, fd(S, F_rho_base), c, k, exner, rb);
+        gather2<LP>(fd(S, F_rtheta_base), c, fd(S, F_exner_base), c, k, rtb, exb);
+        const double gamma_old = colk(fd(S, F_gamma_tri), c);
+        const double coftz_old = k == L ? keepv<LP>(S, F_coftz, KC, c) : 0.0;  // (as vert_imp_body)
+        colk(fw(S, F_w_2), c) = KEEPW(w, keepv<LP>(S, F_w_2, KC, c));
+        const double q_k = 0.0, q_km1 = 0.0, qtotal = 0.5 * (q_k + q_km1);  // (the expressions below)
+        const double cqw = k > L ? 0.0 : 1.0 / (1.0 + qtotal), qtot = 0.0;
+        vi_column<LP, false>(S, c, k, zz, exner, tm, cqw, qtot, rb, rtb, rtp, exb, gamma_old, coftz_old, dtseps, rcv, c2,
+                             true, (copies & 2) != 0, (copies & 4) != 0);
+        return;
+    }
     if (blk >= ncb) {  // :767-771 ru_save = ru, u_2 = u (every level but L)
         const int e = col_of<LP>(xcd_block_n(S.xcd, blk - ncb, bk.n - ncb)) + S.lo[KE];
         if (e >= S.nEO) return;

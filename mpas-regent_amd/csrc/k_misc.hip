@@ -161,13 +161,20 @@ hipError_t launch_moist_coefficients(const DevState& S, hipStream_t st) {
 // makes those copies).  The same values as the three launches.
 // MPAS vertical solver / dynamics (physics 1 / 2): the same fusion with vert_imp's MPAS form,
 // and under the MPAS dynamics setup's theta_m_save and moist's cqu (edge blocks) too
-template <int LP, bool MPASV = false, bool MD = false>
+template <int LP, bool MPASV = false, bool MD = false, bool KEPT = false>
 __global__ __launch_bounds__(256) void k_setup_vi(DevState S, int ncb, double dtseps, double rcv, double c2, int copies) {
-    setup_vi_body<LP, MPASV, MD>(S, ncb, dtseps, rcv, c2, this_blk(), copies);
+    setup_vi_body<LP, MPASV, MD, KEPT>(S, ncb, dtseps, rcv, c2, this_blk(), copies);
 }
 template <int LP>
-static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco) {
+static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco, int kept) {
     if (nco && S.physics) return hipErrorInvalidValue;  // (option accoef: reference semantics only)
+    if (kept) {  // (option stepkeep: w_2 and vert_imp's live columns alone, k_cols.h setup_vi_body KEPT)
+        if (S.physics || S.halo || edges || !nbc || !nco) return hipErrorInvalidValue;
+        const int nb = col_blocks<LP>(S, KC);
+        if (nb) k_setup_vi<LP, false, false, true><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), kRgas / (kCp - kRgas),
+                                                                       kCp * (kRgas / (kCp - kRgas)), 6);
+        return hipGetLastError();
+    }
     double dtseps = vi_dtseps(dts);
     double rcv = kRgas / (kCp - kRgas);
     double c2 = kCp * rcv;
@@ -188,8 +195,35 @@ static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, boo
     if (!nbc) HALO_WROTE(S, F_b_tri, F_c_tri);
     return hipGetLastError();
 }
-hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco) {
-    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco);
+hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco,
+                                       int kept) {
+    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco, kept);
+}
+
+// one cell column copied to another at every level but L, the padding levels included (zeros in both): option
+// stepkeep's copy of the w stage 0's dyn_tend leaves (X_w0 = w) and its restore (w = X_w0; level L of w evolves)
+__global__ __launch_bounds__(256) void k_col_copy(DevState S, int from, int to) {
+    const size_t n = (size_t)S.nCO * S.LP;
+    const double* s = fd(S, from);
+    double* d = fw(S, to);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if (plev(S.LP, (int)(i & (size_t)(S.LP - 1))) == S.L) continue;
+        d[i] = s[i];
+    }
+}
+hipError_t launch_cell_col_copy(const DevState& S, hipStream_t st, int from, int to) {
+    if (S.halo) return hipErrorInvalidValue;  // (undecomposed: no ghost bookkeeping)
+    if (S.LP == 64) {
+        CopyList cl{};
+        cl.src[0] = (const double*)S.f[from];
+        cl.dst[0] = (double*)S.f[to];
+        cl.dst2[0] = nullptr;
+        cl.npair[0] = (size_t)S.nCO * 32;
+        copy64(S, st, cl, 1);
+    } else {
+        k_col_copy<<<stream_grid((size_t)S.nCO * S.LP), 256, 0, st>>>(S, from, to);
+    }
+    return hipGetLastError();
 }
 
 template <int LP, bool MPASV>

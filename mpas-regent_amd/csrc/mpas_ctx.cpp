@@ -63,6 +63,7 @@ const FieldInfo kFields[X_COUNT] = {
     {"Rm", K_C3V, 8, D_M, 0, 0},
     {"su", K_C3V, 8, D_M, 0, 0},
     {"hskv", K_C3, 1, D_M, 0, 0},
+    {"w0", K_C3, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -137,6 +138,21 @@ struct mpas_ctx {
     // the sum's inputs -- u_tend, zb_cell, zb3_cell, edgesOnCell_sign, fzm, fzp, the mesh lists, rw -- have no
     // writer among the step's tasks, so only a call from outside can change them
     bool sml_valid = false;
+    // option "stepkeep" (reference semantics, where stepkeep_active holds): no task of the step
+    // writes u, ru, rw, rho_zz, theta_m, rho_p, rtheta_p, h, zz, exner or the base fields, so most of what a step
+    // stores is what the step before stored.  keep_gen counts the steps completed since the last call from
+    // outside that could have changed a field or the form of the step (0, 1, 2: sml_valid generalised; cleared
+    // where it is cleared, and by a step with another dt or schedule than keep_dt / keep_schedule):
+    //   >= 1 (a full step has run): neither solve_diagnostics launch runs -- their outputs are functions of u
+    //        and h alone --, and the setup launch stores only w_2 and vert_imp's columns (k_setup_vi KEPT);
+    //   2, with stepkeep = 2 only (a generation-1 step has run, whose stage 0 read the step's own diagnostics):
+    //        stage 0's dyn_tend does not run -- everything it stores is final but w, restored from the copy the
+    //        generation-1 step took (X_w0) -- and stage 2 forms tend_u, v and w alone.
+    // 1 is the default; 2 changes which dyn_tend rows a timed step has
+    int stepkeep = 1;
+    int keep_gen = 0;
+    double keep_dt = 0.0;
+    int keep_schedule = -1;
     int fusedamp = 1;  // option "fusedamp": atm_srk3 applies each divergence damping inside the next
                        // acoustic launch (reference semantics, undecomposed; same bits)
     void* raw[X_COUNT] = {};  // the allocations behind S.f (S.f[f] = raw[f] + stagger)
@@ -166,13 +182,14 @@ struct mpas_ctx {
     struct GraphEntry {
         double dt = 0.0;
         int schedule = -1;
+        int gen = 0;  // (option stepkeep: the generation the captured step ran at)
         std::vector<uint8_t> stale0, stale1;
         int64_t exch = 0, fields = 0;
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         uint64_t used = 0;
     };
-    static constexpr size_t kGraphCache = 4;
+    static constexpr size_t kGraphCache = 6;  // (two (dt, schedule) pairs at the three generations of stepkeep)
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     int64_t graph_captures = 0, graph_launches = 0;
@@ -563,7 +580,7 @@ void bounds_check(mpas_ctx*) {}
 template <class Fn>
 int guarded(mpas_ctx* c, Fn&& fn, bool keeps_sml = false) {
     if (!c) return MPAS_EINVAL;
-    if (!keeps_sml) c->sml_valid = false;
+    if (!keeps_sml) c->sml_valid = false, c->keep_gen = 0;
     try {
         fn();
         if (MPAS_BOUNDS) bounds_check(c);
@@ -951,7 +968,21 @@ void sml_ensure(mpas_ctx* c) {
     c->sml_valid = true;
 }
 
-void srk3(mpas_ctx* c, double dt, int schedule) {
+// the rk_step argument of stage s's dyn_tend (Q4: the reference driver passes the stage's time step)
+int srk3_rk_of(double dt, int schedule, int s) {
+    const double sub[3] = {dt / 3, dt / 2, dt / 2};
+    return schedule == 0 ? (int)sub[s] : s;
+}
+// option stepkeep: the step whose launches the kept generation may thin out -- the headline's order
+// (DESIGN.md §4k lists why each condition is there); anywhere else keep_gen stays 0
+bool stepkeep_active(const mpas_ctx* c, double dt, int schedule) {
+    return c->stepkeep && smlkeep_active(c) && c->ntu == 1 && c->defer4 && c->fusesetup && c->fusecopy && c->accoef &&
+           !hfuse_active(c) && !c->tmedge && !c->etile && !c->transport && !c->forcing &&
+           srk3_rk_of(dt, schedule, 0) == 0 && srk3_rk_of(dt, schedule, 1) != 0 && srk3_rk_of(dt, schedule, 2) != 0;
+}
+
+// gen: the kept generation the step runs at (option stepkeep; 0: every launch of the step)
+void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
     // rk_timestep.rg:378-399
     const int number_of_sub_steps = 2;
     const int dynamics_split = 1;  // constants.rg:62
@@ -1092,7 +1123,7 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         const bool nbc = c->ntu == 1 || c->ntu == 2;
         run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
                           : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
-                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco); });
+                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0); });
         dts_vi = rk_sub_timestep[0];
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
@@ -1115,12 +1146,30 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
         if (rk_step == 2) vdyn_on = c->vdyn && S.physics == 0 && a.rk_step > 0 && S.eoe_same;
         a.store_v = (rk_step == 2 && vdyn_on) ? 1 : 0;
         a_done = false;
+        // option stepkeep = 2, generation 2: everything stage 0's dyn_tend stores is in place from the
+        // generation-1 step (whose stage 0 read the diagnostics the step itself formed, as this one would)
+        // -- kdiff, tend_rho, dpdz, ru_save, u_2, the delsq fields, tend_u_euler, tend_w_euler, tend_theta_euler
+        // -- but w, which the acoustic launches and the later stages have rewritten since: restored below
+        // level L from that step's copy.  Stage 2 then forms tend_u, v and w alone: h_divergence (A) and the
+        // theta tendencies (B's flux, E) are final too, and tend_u_euler already holds its del4 part
+        const bool keep2 = gen == 2 && c->stepkeep == 2;
+        if (keep2 && rk_step == 2) {
+            a.skipA = 1;
+            a.defer_in = 0;
+            a.nth = 1;
+        }
         // timing key: the variant's read / write set (bench.py parses the tags)
         const std::string dname = std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") +
                                   (a.cp ? "+copy" : "") + (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") +
                                   (a.store_v ? "+v" : "") + (a.rud != 0.0 ? "+ru" : "") + (a.smlE ? "+sml" : "") +
                                   (a.skipA ? "-A" : "") + "]";
-        run_task(c, dname.c_str(), [&] { return launch_dyn_tend(S, st, a); });
+        if (keep2 && rk_step == 0) {
+            run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
+        } else {
+            run_task(c, dname.c_str(), [&] { return launch_dyn_tend(S, st, a); });
+            if (gen == 1 && c->stepkeep == 2 && rk_step == 0)  // (the copy a generation-2 step restores)
+                run_task(c, "stepkeep_save_w", [&] { return launch_cell_col_copy(S, st, F_w, X_w0); });
+        }
         const bool ru_done = a.rud != 0.0;  // (option mru: the first substep's ru_p / ruAvg stored)
         // option fusesml (with fusedamp): the stage's first acoustic launch runs it first
         const bool sml = fuse && c->fusesml;
@@ -1202,7 +1251,12 @@ void srk3(mpas_ctx* c, double dt, int schedule) {
                 return launch_recover_large_step(S, st, ns_r, rk_step, dt, navg ? 1 : 0, dmp, rk_sub_timestep[rk_step]);
             });
         }
-        if (hf && fuse && rk_step == 2 && S.LP == 64 && !c->transport) {
+        if (gen >= 1) {
+            // option stepkeep: no solve_diagnostics launch -- its outputs are functions of u and h alone, which
+            // no task of the step writes: they hold what the last stage of the step before stored (stage 1's
+            // [live] outputs are bits of that full kernel's, option ntu's own identity; v as stage 2's B or
+            // that kernel stored it)
+        } else if (hf && fuse && rk_step == 2 && S.LP == 64 && !c->transport) {
             // (the vertex / cell kernel ran beside the last damping) the edge kernel beside
             // atm_rk_dynamics_substep_finish, which follows below
             run_task(c, vdyn_on ? (norz ? "hfuse[solve_e-v+finish-rz]" : "hfuse[solve_e-v+finish]")
@@ -1292,21 +1346,21 @@ void prepare_now(mpas_ctx* c) {
     ett_ensure(c);
 }
 
-// one atm_srk3 step: replayed from a captured HIP graph when possible
-void srk3_step(mpas_ctx* c, double dt, int schedule) {
+// one atm_srk3 step at kept generation gen: replayed from a captured HIP graph when possible
+void srk3_run(mpas_ctx* c, double dt, int schedule, int gen) {
     Halo* h = c->halo.get();
     const bool halo_graph = h && !h->loop && (h->stub ? c->graph_halo != 0 : (h->rccl && c->graph_halo == 1)) &&
                             !c->graph_refused;
     sml_ensure(c);
     if (!c->graph_on || c->timing || (h && !halo_graph)) {
-        srk3(c, dt, schedule);
+        srk3(c, dt, schedule, gen);
         return;
     }
     prepare_now(c);  // (synchronous: never inside a capture)
     static const std::vector<uint8_t> none;
     const std::vector<uint8_t>& start = h ? h->stale : none;
     for (auto& g : c->graphs)
-        if (g.dt == dt && g.schedule == schedule && g.stale0 == start) {
+        if (g.dt == dt && g.schedule == schedule && g.gen == gen && g.stale0 == start) {
             hipcheck(hipGraphLaunch(g.exec, c->stream), "hipGraphLaunch");
             g.used = ++c->graph_clock;
             c->graph_launches++;
@@ -1321,12 +1375,13 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
         // a start state not seen before (e.g. the first step after an upload): one eager step
         if (c->seen_stale0.size() >= 16) c->seen_stale0.erase(c->seen_stale0.begin());
         c->seen_stale0.push_back(h->stale);
-        srk3(c, dt, schedule);
+        srk3(c, dt, schedule, gen);
         return;
     }
     mpas_ctx::GraphEntry g;
     g.dt = dt;
     g.schedule = schedule;
+    g.gen = gen;
     g.stale0 = start;
     int64_t ex0 = 0, fl0 = 0;
     if (h) {
@@ -1336,7 +1391,7 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
     }
     hipcheck(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
     try {
-        srk3(c, dt, schedule);
+        srk3(c, dt, schedule, gen);
     } catch (...) {
         hipGraph_t gr = nullptr;
         (void)hipStreamEndCapture(c->stream, &gr);
@@ -1350,7 +1405,7 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
             if (h->capture_miss) {  // a pack table not built yet (never built inside a capture)
                 h->capture_miss = false;
                 h->err.clear();
-                srk3(c, dt, schedule);  // eagerly: builds it; the next step captures
+                srk3(c, dt, schedule, gen);  // eagerly: builds it; the next step captures
                 return;
             }
             // the transport refused the capture (a communicator that cannot be captured):
@@ -1359,7 +1414,7 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
             h->err.clear();
             c->graph_refused = true;
             c->graph_fallbacks++;
-            srk3(c, dt, schedule);
+            srk3(c, dt, schedule, gen);
             return;
         }
         throw;
@@ -1378,7 +1433,7 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
             h->race.clear();
             c->graph_refused = true;
             c->graph_fallbacks++;
-            srk3(c, dt, schedule);
+            srk3(c, dt, schedule, gen);
             return;
         }
         hipcheck(ee, "hipStreamEndCapture");
@@ -1400,6 +1455,22 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
     c->graphs.push_back(g);
     hipcheck(hipGraphLaunch(g.exec, c->stream), "hipGraphLaunch");
     c->graph_launches++;
+}
+
+
+// one atm_srk3 step, with option stepkeep's bookkeeping: the generation the step runs at, then the one it leaves
+void srk3_step(mpas_ctx* c, double dt, int schedule) {
+    const bool act = stepkeep_active(c, dt, schedule);
+    if (!act || c->keep_dt != dt || c->keep_schedule != schedule) c->keep_gen = 0;
+    // (the launches of generations 1 and 2 differ with stepkeep = 2 only: one captured graph for both otherwise)
+    const int gen = (c->keep_gen == 2 && c->stepkeep != 2) ? 1 : c->keep_gen, next = c->keep_gen < 2 ? c->keep_gen + 1 : 2;
+    c->keep_gen = 0;  // (a step that fails promises nothing)
+    srk3_run(c, dt, schedule, gen);
+    if (act) {
+        c->keep_gen = next;
+        c->keep_dt = dt;
+        c->keep_schedule = schedule;
+    }
 }
 
 }  // namespace
@@ -1553,6 +1624,9 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         } else if (name && std::strcmp(name, "smlkeep") == 0) {
             if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "smlkeep must be 0 or 1"};
             c->smlkeep = (int)value;
+        } else if (name && std::strcmp(name, "stepkeep") == 0) {
+            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "stepkeep must be 0, 1 or 2"};
+            c->stepkeep = (int)value;
         }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
@@ -1735,6 +1809,8 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "accoef") == 0) *value = c->accoef;
         else if (name && std::strcmp(name, "dd0") == 0) *value = c->dd0;
         else if (name && std::strcmp(name, "smlkeep") == 0) *value = c->smlkeep;
+        else if (name && std::strcmp(name, "stepkeep") == 0) *value = c->stepkeep;
+        else if (name && std::strcmp(name, "stepkeep_gen") == 0) *value = c->keep_gen;  // (read-only)
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;
         else if (name && std::strcmp(name, "vdyn") == 0) *value = c->vdyn;
@@ -2063,7 +2139,7 @@ int mpas_halo_loopback(mpas_ctx** ctxs, int n) {
     if (!ctxs || n < 1) return MPAS_EINVAL;
     for (int i = 0; i < n; i++)
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) return MPAS_EINVAL;
-    for (int i = 0; i < n; i++) ctxs[i]->sml_valid = false;
+    for (int i = 0; i < n; i++) ctxs[i]->sml_valid = false, ctxs[i]->keep_gen = 0;
     return guarded(ctxs[0], [&] {
         hipcheck(hipSetDevice(ctxs[0]->device), "hipSetDevice");
         auto g = std::make_shared<LoopGroup>();
@@ -2298,7 +2374,7 @@ int mpas_atm_srk3(mpas_ctx* c, double dt, int schedule) {
         if (c->transport == 2) tr_rk_supported(c, "atm_srk3 with transport = 2");  // (never inside a capture)
         srk3_step(c, dt, schedule);
     }, true);
-    if (c && rc != MPAS_OK) c->sml_valid = false;  // (a failed step promises nothing)
+    if (c && rc != MPAS_OK) c->sml_valid = false, c->keep_gen = 0;  // (a failed step promises nothing)
     return rc;
 }
 int mpas_atm_timestep(mpas_ctx* c, double dt) { return mpas_atm_srk3(c, dt, 0); }

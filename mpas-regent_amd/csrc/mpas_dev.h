@@ -106,6 +106,8 @@ enum FieldId {
     // Held-Suarez forcing (k_forcing.hip)
     X_hskv,     // the Rayleigh friction rate kv per cell and level (zeros from level L up): formed by
                 // the task's cell kernel, gathered at the two cells of each edge by its edge kernel   C3
+    X_w0,       // option stepkeep: the w stage 0's dyn_tend left in the last step that ran it (a function of
+                // fields no task of the step writes, below level L), restored by the steps that skip it    C3
     X_COUNT
 };
 
@@ -258,8 +260,13 @@ inline double vi_dtseps(double dts) { return .5 * dts * (1.0 + kEpssm); }
 // (nbc, atm_srk3 option ntu: vert_imp's b_tri / c_tri not stored -- stage 1's vert_imp rewrites them)
 // (nco, atm_srk3 option accoef, reference semantics: nor cofwr / coftz / a_tri -- the acoustic launches
 // of the step form them, and stage 1's vert_imp stores all three)
+// (kept, atm_srk3 option stepkeep, undecomposed, with nbc and nco and without edges: the copies of fields no
+// task of the step writes, and moist's constants, are in place from the step before -- w_2 and vert_imp's
+// live columns alone)
 hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges = true, int nbc = 0,
-                                       int nco = 0);
+                                       int nco = 0, int kept = 0);
+// cell column `to` = cell column `from` at every level but L (option stepkeep: X_w0 and w; undecomposed)
+hipError_t launch_cell_col_copy(const DevState& S, hipStream_t st, int from, int to);
 // option hfuse (atm_srk3, reference semantics, undecomposed): a stage's last acoustic launch
 // (mode 2) beside its solve_diagnostics vertex / cell kernel; the stage's solve_diagnostics
 // edge kernel beside the next stage's dyn_tend A (and stage 1's vert_imp after stage 0)

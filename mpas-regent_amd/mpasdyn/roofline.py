@@ -261,6 +261,9 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
         # cell kernel stores and the edge kernel gathers (X_hskv) takes no credit, as every scratch
         return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "lat", "ru", "cellsOnEdge"],
                 ["tend_rtheta_physics", "tend_ru_physics"])
+    if task in ("stepkeep_restore_w", "stepkeep_save_w"):  # option stepkeep = 2 (no reference task)
+        # one cell column read, one written: w from (to) the scratch copy of the w stage 0's dyn_tend leaves
+        return ["w"], ["w"]
     raise KeyError(task)
 
 
