@@ -172,7 +172,15 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * per-task timing of such a step has no rk_step 0 dyn_tend row.  0: every launch in every step.  A non-finite
  * value in one of those fields then no longer re-enters each step.  Any other value: MPAS_EINVAL.  Read-only
  * "stepkeep_gen": the steps completed since the last call that could have changed a field or the form of
- * the step (0, 1, or 2 for two and more).  "trepw" = 2 (speed only; measured within 2 %, default 1): two
+ * the step (0, 1, or 2 for two and more).  "vikeep" = 1 (default; speed only; exactly where "stepkeep" is
+ * active): every input of atm_compute_vert_imp_coefs is a field no task of the step writes, so each of the
+ * step's two coefficient sets is the same in every consecutive step but for alpha_tri / gamma_tri (the
+ * recurrence over calls).  Stage 0's set is kept in scratch columns -- cofwt, cofwz, cofwr, coftz, a_tri, b_tri
+ * and c_tri hold stage 1's after any step, as before -- and a step at "stepkeep_gen" >= 1 forms alpha_tri and
+ * gamma_tri alone, from the stored a, b, c and the gamma_tri it finds.  Such a step also runs stage 2's
+ * dyn_tend without the kernel that stores h_divergence (a function of ru and the mesh), with or without
+ * "vikeep".  Every field bit-identical; 0: both sets formed in every step.  Any other value: MPAS_EINVAL.
+ * "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of
  * compact cell tiles in LDS and no edge scratch, when every cell has at most 6 edges with

@@ -54,13 +54,42 @@ __device__ __forceinline__ double vi_a_tri(double cofwz, double coftz_m, double 
     return -1.0 * cofwz * coftz_m * rdzw_m * zz_m + cofwr * cofrz_m - cofwt_m * coftz_m * rdzw_m;
 }
 
+// alpha_tri and gamma_tri of the reference form (:580-591) from the call's a, b, c and the gamma_tri the
+// call found (Q17: the stale gamma of level k - 1, 0.0 for level 0's, which the call has just zeroed), then
+// the values their stores write at level k (the slots the reference leaves keep their values).  vi_column
+// and the kept forms (option vikeep: a, b, c loaded instead of formed) share this text, so one operation
+// order.  Every lane of the column calls vi_alpha_gamma (a shuffle)
+template <int LP>
+__device__ __forceinline__ void vi_alpha_gamma(double a, double b, double cc, double gamma_old, int k, double& alpha,
+                                               double& gamma) {
+    const double gamma_dn = lvl_dn<LP>(gamma_old, k);  // shuffle outside any branch
+    const double gamma_m = (k == 1) ? 0.0 : gamma_dn;  // Q17: gamma(0) was just zeroed
+    alpha = 1.0 / (b - a * gamma_m);  // :580-585
+    gamma = cc * alpha;               // :587-591
+}
+template <int LP>
+__device__ __forceinline__ double vi_alpha_st(const DevState& S, int c, int k, double alpha) {
+    const int L = S.L;
+    return KEEPW0(alpha, keepv<LP>(S, F_alpha_tri, KC, c, true), keepv<LP>(S, F_alpha_tri, KC, c));
+}
+template <int LP>
+__device__ __forceinline__ double vi_gamma_st(const DevState& S, int c, int k, double gamma) {
+    const int L = S.L;
+    return k == 0 ? 0.0 : KEEPW(gamma, keepv<LP>(S, F_gamma_tri, KC, c));
+}
+
 // one column of atm_compute_vert_imp_coefs from its loaded inputs (k_vert_imp, and the
 // stage-0 fusion with the setup copies and the moist coefficients, k_setup_vi)
 template <int LP, bool MPASV>
 __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, double zz, double exner, double tm, double cqw,
                                           double qtot, double rb, double rtb, double rtp, double exb, double gamma_old,
                                           double coftz_old, double dtseps, double rcv, double c2, bool live = true,
-                                          bool nbc = false, bool nco = false) {
+                                          bool nbc = false, bool nco = false, bool vk = false) {
+    // (vk, atm_srk3 option vikeep, with nbc and nco: stage 0's set is the same bits in every consecutive step
+    // and nothing reads cofwt / cofwz as fields before stage 1's vert_imp rewrites both -- the pair goes to
+    // X_cofwt0 / X_cofwz0, with the bytes the fields would hold at every position, where stage 0's acoustic
+    // launches load it; a, b and c as computed go to X_a0 / X_b0 / X_c0 for the kept setup launch.  The
+    // fields keep stage 1's set)
     // (nbc, atm_srk3 option ntu: stage 0's vert_imp -- b_tri and c_tri are dead there: stage 1's vert_imp
     // rewrites both and no task reads them in between, nor does that vert_imp; not stored)
     // (nco, atm_srk3 option accoef: stage 0's vert_imp -- cofwr, coftz and a_tri are dead there too: only the
@@ -86,8 +115,6 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     }
     const double coftz_m = lvl_dn<LP>(coftz, k), coftz_p = lvl_up<LP>(coftz, k);
     const double cofwt_m = lvl_dn<LP>(cofwt, k);
-    const double gamma_dn = lvl_dn<LP>(gamma_old, k);  // shuffle outside any branch
-    const double gamma_m = (k == 1) ? 0.0 : gamma_dn;  // Q17: gamma(0) was just zeroed
     const double cofrz = dtseps * rdzw, cofrz_m = dtseps * rdzw_m;      // :537-539
 
     // :566-578 (every lane; used at 0 < k < L)
@@ -127,8 +154,7 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
         alpha = in ? s_a[j][k] : 0.0;
         gamma = in ? s_c[j][k] : 0.0;
     } else {
-        alpha = 1.0 / (b - a * gamma_m);  // :580-585
-        gamma = cc * alpha;               // :587-591
+        vi_alpha_gamma<LP>(a, b, cc, gamma_old, k, alpha, gamma);
     }
 
     // written: every level but L (padding levels: zeros, full 64-B sectors; see PADW); the
@@ -138,9 +164,14 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     // written with their kept values: keep tails, mpas_dev.h; every line of a column whole)
     auto kL = [&](int f) { return keepv<LP>(S, f, KC, c); };
     auto k0 = [&](int f) { return keepv<LP>(S, f, KC, c, true); };
+    const double alpha_st = vi_alpha_st<LP>(S, c, k, alpha), gamma_st = vi_gamma_st<LP>(S, c, k, gamma);
     if (nco) {  // (the two coefficients the acoustic step still loads, paired)
-        put2<LP>(fw(S, F_cofwt), c, fw(S, F_cofwz), c, k, KEEPW(cofwt, kL(F_cofwt)),
+        put2<LP>(fw(S, vk ? X_cofwt0 : F_cofwt), c, fw(S, vk ? X_cofwz0 : F_cofwz), c, k, KEEPW(cofwt, kL(F_cofwt)),
                  KEEPW0(cofwz, k0(F_cofwz), kL(F_cofwz)), live, live);
+        if (vk) {  // (whole columns, as computed: the kept launch uses levels 1 .. L - 1)
+            put2<LP>(fw(S, X_a0), c, fw(S, X_b0), c, k, a, b, live, live);
+            if (live) colk(fw(S, X_c0), c) = cc;
+        }
     } else {
         put2<LP>(fw(S, F_coftz), c, fw(S, F_cofwt), c, k, KEEPW(coftz, kL(F_coftz)), KEEPW(cofwt, kL(F_cofwt)), live, live);
         put2<LP>(fw(S, F_cofwr), c, fw(S, F_cofwz), c, k, KEEPW0(cofwr, k0(F_cofwr), kL(F_cofwr)),
@@ -149,19 +180,19 @@ __device__ __forceinline__ void vi_column(const DevState& S, int c, int k, doubl
     if (nbc) {
         if (live) {
             if (!nco) colk(fw(S, F_a_tri), c) = KEEPW0(a, k0(F_a_tri), kL(F_a_tri));
-            colk(fw(S, F_alpha_tri), c) = KEEPW0(alpha, k0(F_alpha_tri), kL(F_alpha_tri));
+            colk(fw(S, F_alpha_tri), c) = alpha_st;
         }
     } else if (nco) {
         if (live) colk(fw(S, F_b_tri), c) = KEEPW0(b, k0(F_b_tri), kL(F_b_tri));
         put2<LP>(fw(S, F_c_tri), c, fw(S, F_alpha_tri), c, k, KEEPW0(cc, k0(F_c_tri), kL(F_c_tri)),
-                 KEEPW0(alpha, k0(F_alpha_tri), kL(F_alpha_tri)), live, live);
+                 alpha_st, live, live);
     } else {
         put2<LP>(fw(S, F_a_tri), c, fw(S, F_b_tri), c, k, KEEPW0(a, k0(F_a_tri), kL(F_a_tri)),
                  KEEPW0(b, k0(F_b_tri), kL(F_b_tri)), live, live);
         put2<LP>(fw(S, F_c_tri), c, fw(S, F_alpha_tri), c, k, KEEPW0(cc, k0(F_c_tri), kL(F_c_tri)),
-                 KEEPW0(alpha, k0(F_alpha_tri), kL(F_alpha_tri)), live, live);
+                 alpha_st, live, live);
     }
-    if (live) colk(fw(S, F_gamma_tri), c) = k == 0 ? 0.0 : KEEPW(gamma, kL(F_gamma_tri));
+    if (live) colk(fw(S, F_gamma_tri), c) = gamma_st;
     if (live && c == 0 && k < L) fw(S, F_cofrz)[k] = cofrz;
 }
 
@@ -184,6 +215,25 @@ __device__ __forceinline__ void vert_imp_body(const DevState& S, double dtseps, 
     const double coftz_old = k == S.L ? keepv<LP>(S, F_coftz, KC, c) : 0.0;
     vi_column<LP, MPASV>(S, c, k, zz, exner, tm, cqw, qtot, rb, rtb, rtp, exb, gamma_old, coftz_old, dtseps, rcv, c2,
                          live);
+}
+
+// atm_srk3 option vikeep, stage 1's vert_imp of a kept step (reference semantics): every input of the call is a
+// field no task of the step writes, so cofwt, cofwz, cofwr, coftz, a_tri, b_tri and c_tri hold what the call would
+// store -- the last full step's stage-1 call stored them and nothing has written them since (stage 0's set lives
+// in scratch).  Left: alpha_tri and gamma_tri (gamma_tri's recurrence over calls, Q17) from the stored a, b, c,
+// and cofrz.  Four loads in two pairs, one paired store
+template <int LP>
+__device__ __forceinline__ void vert_imp_kept_body(const DevState& S, double dtseps, Blk bk) {
+    ColMap<LP> m(S, KC, bk);
+    const int L = S.L, k = m.k, c = m.ent;
+    if (c >= S.nCO) return;
+    double a, b, cc, gamma_old, alpha, gamma;
+    gather2<LP>(fd(S, F_a_tri), c, fd(S, F_b_tri), c, k, a, b);
+    gather2<LP>(fd(S, F_c_tri), c, fd(S, F_gamma_tri), c, k, cc, gamma_old);
+    vi_alpha_gamma<LP>(a, b, cc, gamma_old, k, alpha, gamma);
+    put2f<LP>(fw(S, F_alpha_tri), c, fw(S, F_gamma_tri), c, k, vi_alpha_st<LP>(S, c, k, alpha),
+              vi_gamma_st<LP>(S, c, k, gamma));
+    if (c == 0 && k < L) fw(S, F_cofrz)[k] = dtseps * fd(S, F_rdzw)[k];  // :537-539 (as vi_column)
 }
 
 
@@ -566,13 +616,30 @@ __device__ __forceinline__ void sml_flux_body(const DevState& S, Blk bk) {
 // launch would store -- none of them is stored, and rw, rho_p and rho_zz are not loaded.  Left: w_2 = w (level
 // L of w evolves) and vert_imp (gamma_tri's recurrence over calls, Q17), with qtot / cqw as the constants
 // moist writes; the nine remaining loads paired again with no dead half.  Cell blocks only, copies = 6
-template <int LP, bool MPASV = false, bool MD = false, bool KEPT = false>
+// KEPT 2 (option vikeep on top): vert_imp's a, b and c of this call are the same bits in every such step too
+// (functions of zz, exner, theta_m, rtheta_p and the base fields), and the full launch left them in X_a0 / X_b0 /
+// X_c0 and cofwt / cofwz in X_cofwt0 / X_cofwz0: five loads -- w with a, b with c, gamma_tri -- and three stores,
+// w_2 with alpha_tri and gamma_tri; cofrz as every form
+template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0>
 __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double dtseps, double rcv, double c2, Blk bk,
                                               int copies = 1) {
     static_assert(!KEPT || (!MPASV && !MD), "the kept setup: reference semantics");
     const int L = S.L, k = (int)(threadIdx.x % LP);
     int blk = bk.b;
-    if constexpr (KEPT) {
+    if constexpr (KEPT == 2) {
+        const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
+        if (c >= S.nCO) return;
+        double w, a, b, cc, alpha, gamma;
+        gather2<LP>(fd(S, F_w), c, fd(S, X_a0), c, k, w, a);
+        gather2<LP>(fd(S, X_b0), c, fd(S, X_c0), c, k, b, cc);
+        const double gamma_old = colk(fd(S, F_gamma_tri), c);
+        vi_alpha_gamma<LP>(a, b, cc, gamma_old, k, alpha, gamma);
+        put2f<LP>(fw(S, F_w_2), c, fw(S, F_alpha_tri), c, k, KEEPW(w, keepv<LP>(S, F_w_2, KC, c)),
+                  vi_alpha_st<LP>(S, c, k, alpha));
+        colk(fw(S, F_gamma_tri), c) = vi_gamma_st<LP>(S, c, k, gamma);
+        if (c == 0 && k < L) fw(S, F_cofrz)[k] = dtseps * fd(S, F_rdzw)[k];  // :537-539 (as vi_column)
+        return;
+    } else if constexpr (KEPT == 1) {
         const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
         if (c >= S.nCO) return;
         double rtp, w, tm, zz, exner, rb, rtb, exb;
@@ -636,6 +703,7 @@ __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double
     // (cqw is used at 0 < k < L only, qtot at k < L: the values just written)
     vi_column<LP, MPASV>(S, c, k, zz, exner, tm, cqw, qtot, rb, rtb, rtp, exb, gamma_old, coftz_old, dtseps, rcv, c2,
                          live, (copies & 2) != 0,   // (copies bit 1: b_tri / c_tri dead, atm_srk3 option ntu)
-                         (copies & 4) != 0);        // (bit 2: cofwr / coftz / a_tri dead, option accoef)
+                         (copies & 4) != 0,         // (bit 2: cofwr / coftz / a_tri dead, option accoef)
+                         (copies & 8) != 0);        // (bit 3: the set to scratch, option vikeep)
 }
 }  // namespace mpas

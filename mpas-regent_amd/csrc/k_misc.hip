@@ -161,18 +161,22 @@ hipError_t launch_moist_coefficients(const DevState& S, hipStream_t st) {
 // makes those copies).  The same values as the three launches.
 // MPAS vertical solver / dynamics (physics 1 / 2): the same fusion with vert_imp's MPAS form,
 // and under the MPAS dynamics setup's theta_m_save and moist's cqu (edge blocks) too
-template <int LP, bool MPASV = false, bool MD = false, bool KEPT = false>
+template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0>
 __global__ __launch_bounds__(256) void k_setup_vi(DevState S, int ncb, double dtseps, double rcv, double c2, int copies) {
     setup_vi_body<LP, MPASV, MD, KEPT>(S, ncb, dtseps, rcv, c2, this_blk(), copies);
 }
 template <int LP>
-static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco, int kept) {
+static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco, int kept,
+                              int vik) {
     if (nco && S.physics) return hipErrorInvalidValue;  // (option accoef: reference semantics only)
+    // (option vikeep: the set in scratch -- the conditions of the kept launch, in the full launch too)
+    if (vik && (S.physics || S.halo || edges || !nbc || !nco)) return hipErrorInvalidValue;
     if (kept) {  // (option stepkeep: w_2 and vert_imp's live columns alone, k_cols.h setup_vi_body KEPT)
         if (S.physics || S.halo || edges || !nbc || !nco) return hipErrorInvalidValue;
         const int nb = col_blocks<LP>(S, KC);
-        if (nb) k_setup_vi<LP, false, false, true><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), kRgas / (kCp - kRgas),
-                                                                       kCp * (kRgas / (kCp - kRgas)), 6);
+        const double rcv = kRgas / (kCp - kRgas);
+        if (nb && vik) k_setup_vi<LP, false, false, 2><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), rcv, kCp * rcv, 14);
+        else if (nb) k_setup_vi<LP, false, false, 1><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), rcv, kCp * rcv, 6);
         return hipGetLastError();
     }
     double dtseps = vi_dtseps(dts);
@@ -180,7 +184,7 @@ static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, boo
     double c2 = kCp * rcv;
     const bool md = S.physics == 2;
     const int ncb = col_blocks<LP>(S, KC), neb = (edges || md) ? col_blocks<LP>(S, KE) : 0;
-    const int cp = (edges ? 1 : 0) | (nbc ? 2 : 0) | (nco ? 4 : 0);
+    const int cp = (edges ? 1 : 0) | (nbc ? 2 : 0) | (nco ? 4 : 0) | (vik ? 8 : 0);
     if (ncb + neb) {
         if (md) k_setup_vi<LP, true, true><<<ncb + neb, 256, 0, st>>>(S, ncb, dtseps, rcv, c2, cp);
         else if (S.physics) k_setup_vi<LP, true, false><<<ncb + neb, 256, 0, st>>>(S, ncb, dtseps, rcv, c2, cp);
@@ -190,14 +194,15 @@ static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, boo
     if (edges) HALO_WROTE(S, F_ru_save, F_u_2);
     HALO_WROTE(S, F_rw_save, F_rtheta_p_save, F_rho_p_save, F_w_2, F_theta_m_2, F_rho_zz_2, F_rho_zz_old_split, F_qtot,
                F_cqw);
-    HALO_WROTE(S, F_cofwt, F_gamma_tri, F_cofwz, F_alpha_tri);
+    if (vik) HALO_WROTE(S, F_gamma_tri, F_alpha_tri);  // (undecomposed: no bookkeeping either way)
+    else HALO_WROTE(S, F_cofwt, F_gamma_tri, F_cofwz, F_alpha_tri);
     if (!nco) HALO_WROTE(S, F_coftz, F_cofwr, F_a_tri);
     if (!nbc) HALO_WROTE(S, F_b_tri, F_c_tri);
     return hipGetLastError();
 }
 hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco,
-                                       int kept) {
-    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco, kept);
+                                       int kept, int vik) {
+    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco, kept, vik);
 }
 
 // one cell column copied to another at every level but L, the padding levels included (zeros in both): option
@@ -243,6 +248,21 @@ static hipError_t vert_imp_lp(const DevState& S, hipStream_t st, double dts) {
 }
 hipError_t launch_vert_imp_coefs(const DevState& S, hipStream_t st, double dts) {
     MPAS_LP_DISPATCH(S.LP, vert_imp_lp, S, st, dts);
+}
+// (option vikeep: alpha_tri, gamma_tri and cofrz from the stored a_tri, b_tri, c_tri; k_cols.h vert_imp_kept_body)
+template <int LP>
+__global__ __launch_bounds__(256) void k_vert_imp_kept(DevState S, double dtseps) {
+    vert_imp_kept_body<LP>(S, dtseps, this_blk());
+}
+template <int LP>
+static hipError_t vert_imp_kept_lp(const DevState& S, hipStream_t st, double dts) {
+    if (S.physics || S.halo) return hipErrorInvalidValue;
+    const int grid = col_blocks<LP>(S, KC);
+    if (grid) k_vert_imp_kept<LP><<<grid, 256, 0, st>>>(S, vi_dtseps(dts));
+    return hipGetLastError();
+}
+hipError_t launch_vert_imp_kept(const DevState& S, hipStream_t st, double dts) {
+    MPAS_LP_DISPATCH(S.LP, vert_imp_kept_lp, S, st, dts);
 }
 
 // ---------------------------------------------------------------- set_smlstep

@@ -64,6 +64,11 @@ const FieldInfo kFields[X_COUNT] = {
     {"su", K_C3V, 8, D_M, 0, 0},
     {"hskv", K_C3, 1, D_M, 0, 0},
     {"w0", K_C3, 1, D_M, 0, 0},
+    {"cofwt0", K_C3, 1, D_M, 0, 0},
+    {"cofwz0", K_C3, 1, D_M, 0, 0},
+    {"a0", K_C3, 1, D_M, 0, 0},
+    {"b0", K_C3, 1, D_M, 0, 0},
+    {"c0", K_C3, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -148,8 +153,16 @@ struct mpas_ctx {
     //   2, with stepkeep = 2 only (a generation-1 step has run, whose stage 0 read the step's own diagnostics):
     //        stage 0's dyn_tend does not run -- everything it stores is final but w, restored from the copy the
     //        generation-1 step took (X_w0) -- and stage 2 forms tend_u, v and w alone.
+    //   >= 1 also: stage 2's dyn_tend runs without its kernel A -- at rk_step > 0 A stores h_divergence alone, a
+    //        function of ru and the mesh, final from the full step on (its row keeps its tags, with -A)
     // 1 is the default; 2 changes which dyn_tend rows a timed step has
     int stepkeep = 1;
+    // option "vikeep" (where stepkeep is active): vert_imp's two coefficient sets -- stage 0's, dts
+    // = dt / 3, and stage 1's -- are functions of fields no task of the step writes, but for alpha_tri / gamma_tri
+    // (Q17's stale gamma).  Stage 0's set lives in scratch (X_cofwt0, X_cofwz0, X_a0, X_b0, X_c0) in every
+    // generation, so the fields keep stage 1's; at keep_gen >= 1 both launches form alpha_tri / gamma_tri alone
+    // from the stored a, b, c.  Invalidation is keep_gen's: a full step rewrites every one of them first
+    int vikeep = 1;
     int keep_gen = 0;
     double keep_dt = 0.0;
     int keep_schedule = -1;
@@ -1098,6 +1111,8 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
     // launch of that form would lose a wave of occupancy to the three expressions, profiles/r08)
     const int aco = (c->accoef && S.physics == 0 && !tme) ? 1 : 0;
     double dts_vi = 0.0;
+    // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
+    const bool vik = c->vikeep && stepkeep_active(c, dt, schedule);
     bool flux_done = false;  // (option smlsum: the step's flux sum, beside setup and A on small grids)
     // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
     // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
@@ -1123,7 +1138,8 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         const bool nbc = c->ntu == 1 || c->ntu == 2;
         run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
                           : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
-                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0); });
+                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0,
+                                                           vik ? 1 : 0); });
         dts_vi = rk_sub_timestep[0];
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
@@ -1135,7 +1151,11 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st, ddx == 2 ? 2 : 0); });
     for (int rk_step = 0; rk_step < 3; rk_step++) {  // :426-477
         if (rk_step == 1 && !vi_done) {
-            run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[rk_step]); });
+            // (option vikeep, a kept step: a_tri, b_tri, c_tri and the four cof columns hold this call's values)
+            run_task(c, "atm_compute_vert_imp_coefs", [&] {
+                return vik && gen >= 1 ? launch_vert_imp_kept(S, st, rk_sub_timestep[rk_step])
+                                       : launch_vert_imp_coefs(S, st, rk_sub_timestep[rk_step]);
+            });
             dts_vi = rk_sub_timestep[rk_step];
         }
         DynTendArgs a = stage_args(rk_step);
@@ -1158,6 +1178,9 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
             a.defer_in = 0;
             a.nth = 1;
         }
+        // option stepkeep, any kept step: stage 2's A (rk_step > 0: h_divergence alone, from ru and the mesh --
+        // no task of the step writes ru) stored the same bits in the full step; B reads them
+        if (gen >= 1 && rk_step == 2) a.skipA = 1;
         // timing key: the variant's read / write set (bench.py parses the tags)
         const std::string dname = std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") +
                                   (a.cp ? "+copy" : "") + (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") +
@@ -1199,9 +1222,14 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
                     const std::string an = nst ? std::string(acoustic_name(small_step, pending, sm, !(wold & 1))).insert(
                                                      std::strlen(acoustic_name(small_step, pending, sm, !(wold & 1))) - 1, "-st")
                                                : std::string(acoustic_name(small_step, pending, sm, !(wold & 1)));
-                    run_task(c, an.c_str(),
-                             [&] { return launch_acoustic(S, st, dts, small_step, c->exact, mode, coef_prev, tme, sm, wold,
-                                                          ddx, 0, 0, aco, dts_vi); });
+                    run_task(c, an.c_str(), [&] {
+                        // option vikeep: stage 0's launches load cofwt / cofwz from the scratch pair -- a copy of
+                        // the state whose two field slots point there (the kernels are the same)
+                        DevState A = S;
+                        if (vik && rk_step == 0) A.f[F_cofwt] = S.f[X_cofwt0], A.f[F_cofwz] = S.f[X_cofwz0];
+                        return launch_acoustic(A, st, dts, small_step, c->exact, mode, coef_prev, tme, sm, wold, ddx, 0, 0,
+                                               aco, dts_vi);
+                    });
                 }
                 if (mode == 2) fb.swap_rup();
                 fb.swap_dv();  // this substep's div is read next from X_dvB
@@ -1627,6 +1655,9 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         } else if (name && std::strcmp(name, "stepkeep") == 0) {
             if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "stepkeep must be 0, 1 or 2"};
             c->stepkeep = (int)value;
+        } else if (name && std::strcmp(name, "vikeep") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "vikeep must be 0 or 1"};
+            c->vikeep = (int)value;
         }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
@@ -1810,6 +1841,7 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "dd0") == 0) *value = c->dd0;
         else if (name && std::strcmp(name, "smlkeep") == 0) *value = c->smlkeep;
         else if (name && std::strcmp(name, "stepkeep") == 0) *value = c->stepkeep;
+        else if (name && std::strcmp(name, "vikeep") == 0) *value = c->vikeep;
         else if (name && std::strcmp(name, "stepkeep_gen") == 0) *value = c->keep_gen;  // (read-only)
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;

@@ -108,6 +108,13 @@ enum FieldId {
                 // the task's cell kernel, gathered at the two cells of each edge by its edge kernel   C3
     X_w0,       // option stepkeep: the w stage 0's dyn_tend left in the last step that ran it (a function of
                 // fields no task of the step writes, below level L), restored by the steps that skip it    C3
+    // option vikeep: stage 0's vert_imp coefficient set (dts = dt / 3), a function of fields no task of the
+    // step writes; the full setup launch stores it here, not in the fields, which keep stage 1's set
+    X_cofwt0,   // cofwt, cofwz: what stage 0's acoustic launches load (every position of the column as the
+    X_cofwz0,   // fields would hold it, levels 0 / L and the padding included)                            C3
+    X_a0,       // a_tri, b_tri, c_tri as computed (used at 0 < k < L): the kept setup launch forms
+    X_b0,       // alpha_tri and gamma_tri from them and the previous gamma_tri                             C3
+    X_c0,
     X_COUNT
 };
 
@@ -263,8 +270,14 @@ inline double vi_dtseps(double dts) { return .5 * dts * (1.0 + kEpssm); }
 // (kept, atm_srk3 option stepkeep, undecomposed, with nbc and nco and without edges: the copies of fields no
 // task of the step writes, and moist's constants, are in place from the step before -- w_2 and vert_imp's
 // live columns alone)
+// (vik, atm_srk3 option vikeep, with kept's conditions: the launch's coefficient set lives in scratch -- the full
+// launch stores cofwt / cofwz to X_cofwt0 / X_cofwz0, not the fields, and a / b / c to X_a0 / X_b0 / X_c0;
+// the kept launch loads w, those three and gamma_tri and stores w_2, alpha_tri and gamma_tri alone)
 hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges = true, int nbc = 0,
-                                       int nco = 0, int kept = 0);
+                                       int nco = 0, int kept = 0, int vik = 0);
+// atm_srk3 option vikeep, a kept step's stage-1 vert_imp (reference semantics, undecomposed): a_tri, b_tri and
+// c_tri hold this call's values from the last full step -- alpha_tri, gamma_tri and cofrz alone
+hipError_t launch_vert_imp_kept(const DevState& S, hipStream_t st, double dts);
 // cell column `to` = cell column `from` at every level but L (option stepkeep: X_w0 and w; undecomposed)
 hipError_t launch_cell_col_copy(const DevState& S, hipStream_t st, int from, int to);
 // option hfuse (atm_srk3, reference semantics, undecomposed): a stage's last acoustic launch
