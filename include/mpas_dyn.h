@@ -180,6 +180,14 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * gamma_tri alone, from the stored a, b, c and the gamma_tri it finds.  Such a step also runs stage 2's
  * dyn_tend without the kernel that stores h_divergence (a function of ru and the mesh), with or without
  * "vikeep".  Every field bit-identical; 0: both sets formed in every step.  Any other value: MPAS_EINVAL.
+ * "a0keep" = 1 (default; speed only; exactly where "stepkeep" is active): what stage 0's dyn_tend stores in its
+ * first cell kernel -- tend_rho, dpdz, ru_save, u_2 -- is a function of fields no task of the step writes, but
+ * for kdiff, which reads v.  A full step ends with one launch that forms the next step's kdiff in a scratch
+ * column (timing key "a0keep_kdiff"; the field keeps the step's own); a step at "stepkeep_gen" >= 1 takes kdiff
+ * from there, runs stage 0's dyn_tend without that kernel (its row tagged -A) and
+ * atm_rk_dynamics_substep_finish without its edge part (ruAvg has no writer, so ruAvg_split = ruAvg is in
+ * place).  Every field bit-identical; 0: every one of those launches in every step.  Any other value:
+ * MPAS_EINVAL.
  * "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of

@@ -620,28 +620,39 @@ __device__ __forceinline__ void sml_flux_body(const DevState& S, Blk bk) {
 // (functions of zz, exner, theta_m, rtheta_p and the base fields), and the full launch left them in X_a0 / X_b0 /
 // X_c0 and cofwt / cofwz in X_cofwt0 / X_cofwz0: five loads -- w with a, b with c, gamma_tri -- and three stores,
 // w_2 with alpha_tri and gamma_tri; cofrz as every form
-template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0>
+// KD (option a0keep, either kept form): the step's stage 0 runs no dyn_tend A, and the kdiff that A would store
+// -- another one than the field holds after a full step, whose stage 2 replaced v -- sits in X_kd0 (formed by the
+// last launch of the full step, k_dyn.hip launch_dyn_A_kdiff): kdiff = X_kd0 at every position A stores, level
+// L from kdiff's keep tail, zeros on the padding.  KEPT 2 pairs the load with gamma_tri's and the store with
+// gamma_tri's: ten columns for eight, in the same five memory instructions
+template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0, bool KD = false>
 __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double dtseps, double rcv, double c2, Blk bk,
                                               int copies = 1) {
     static_assert(!KEPT || (!MPASV && !MD), "the kept setup: reference semantics");
+    static_assert(!KD || KEPT, "kdiff from scratch: a kept launch");
     const int L = S.L, k = (int)(threadIdx.x % LP);
     int blk = bk.b;
     if constexpr (KEPT == 2) {
         const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
         if (c >= S.nCO) return;
-        double w, a, b, cc, alpha, gamma;
+        double w, a, b, cc, alpha, gamma, gamma_old, kd = 0.0;
         gather2<LP>(fd(S, F_w), c, fd(S, X_a0), c, k, w, a);
         gather2<LP>(fd(S, X_b0), c, fd(S, X_c0), c, k, b, cc);
-        const double gamma_old = colk(fd(S, F_gamma_tri), c);
+        if constexpr (KD) gather2<LP>(fd(S, F_gamma_tri), c, fd(S, X_kd0), c, k, gamma_old, kd);
+        else gamma_old = colk(fd(S, F_gamma_tri), c);
         vi_alpha_gamma<LP>(a, b, cc, gamma_old, k, alpha, gamma);
         put2f<LP>(fw(S, F_w_2), c, fw(S, F_alpha_tri), c, k, KEEPW(w, keepv<LP>(S, F_w_2, KC, c)),
                   vi_alpha_st<LP>(S, c, k, alpha));
-        colk(fw(S, F_gamma_tri), c) = vi_gamma_st<LP>(S, c, k, gamma);
+        if constexpr (KD)
+            put2f<LP>(fw(S, F_gamma_tri), c, fw(S, F_kdiff), c, k, vi_gamma_st<LP>(S, c, k, gamma),
+                      KEEPW(kd, keepv<LP>(S, F_kdiff, KC, c)));
+        else colk(fw(S, F_gamma_tri), c) = vi_gamma_st<LP>(S, c, k, gamma);
         if (c == 0 && k < L) fw(S, F_cofrz)[k] = dtseps * fd(S, F_rdzw)[k];  // :537-539 (as vi_column)
         return;
     } else if constexpr (KEPT == 1) {
         const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
         if (c >= S.nCO) return;
+        if constexpr (KD) colk(fw(S, F_kdiff), c) = KEEPW(colk(fd(S, X_kd0), c), keepv<LP>(S, F_kdiff, KC, c));
         double rtp, w, tm, zz, exner, rb, rtb, exb;
         gather2<LP>(fd(S, F_rtheta_p), c, fd(S, F_w), c, k, rtp, w);
         gather2<LP>(fd(S, F_theta_m), c, fd(S, F_zz), c, k, tm, zz);

@@ -1609,6 +1609,9 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     // and A runs in this call with the Smagorinsky gathers of u (undecomposed: A's cells own every edge but
     // X_orph's); every other path keeps the copy in B
     a.cpA = (!MD && a.cp && rk0 && ntu && nth && !et && !in.skipA && !S.halo && a.horiz_mixing == 0) ? 1 : 0;
+    // (in.keptA, atm_srk3 option a0keep: A's stores of an earlier call of this form are in place, the copies
+    // included -- no A, no k_dyn_cp_orph, and B the NCP instance as if A had just run; only that form)
+    if (in.keptA && !a.cpA) return hipErrorInvalidValue;
     auto kB = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KE);
         if (!nb) return;
@@ -1770,7 +1773,7 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     // halo: fields each kernel gathers through an index array / fields it writes
     // (u and v only for the Smagorinsky deformation of rk_step 0: a gather declared but not
     // made would cost an exchange whenever v is stale)
-    if (in.skipA) {  // (A ran in the previous combined launch, atm_srk3 hfuse; no halo)
+    if (in.skipA || in.keptA) {  // (A ran in the previous combined launch, atm_srk3 hfuse, or its stores are kept)
     } else if (ntu && !rk0) {  // (A's one output at rk_step > 0, h_divergence, feeds only the dead tend_u)
     } else if (rk0 && a.horiz_mixing == 0) {
         HALO_RUN(S, st, kA, F_ru, F_u, F_v);
@@ -1850,6 +1853,27 @@ static hipError_t dyn_lp(const DevState& S, hipStream_t st, const DynTendArgs& i
 }
 hipError_t launch_dyn_tend(const DevState& S, hipStream_t st, const DynTendArgs& in) {
     MPAS_LP_DISPATCH(S.LP, dyn_lp, S, st, in);
+}
+
+// option "a0keep" (atm_srk3, reference semantics, undecomposed): the last launch of a full step forms the
+// kdiff stage 0's A of the next step would store -- that step skips A -- from u and the v stage 2 has left.
+// The kernel is the plain rk_step 0 A (its kdiff expressions are the CPA instance's: the same loads, masks
+// and order), run on a copy of the state whose kdiff slot points at the scratch column `to`: KEEPW's level-L
+// value then comes from that column's own tail, and the reader of the column (setup_vi_body KEPT) takes level L
+// from the field's.  tend_rho, dpdz and X_wc are stored again with the bytes they hold
+template <int LP>
+static hipError_t dyn_A_kdiff_lp(const DevState& S, hipStream_t st, const DynTendArgs& in, int to) {
+    if (S.halo || S.physics || in.rk_step != 0 || in.horiz_mixing != 0) return hipErrorInvalidValue;
+    const DynK a = make_dynk(S, in);
+    if (!a.nhd) return hipErrorInvalidValue;  // (h_divergence holds stage 2's value by now: not to be stored)
+    DevState X = S;
+    X.f[F_kdiff] = S.f[to];
+    const int nb = col_blocks<LP>(X, KC);
+    if (nb) k_dyn_A<LP, true, false><<<nb, 256, 0, st>>>(X, a);
+    return hipGetLastError();
+}
+hipError_t launch_dyn_A_kdiff(const DevState& S, hipStream_t st, const DynTendArgs& stage0, int to) {
+    MPAS_LP_DISPATCH(S.LP, dyn_A_kdiff_lp, S, st, stage0, to);
 }
 
 // option "hfuse" (atm_srk3, reference semantics, undecomposed): the next stage's dyn_tend A

@@ -161,22 +161,26 @@ hipError_t launch_moist_coefficients(const DevState& S, hipStream_t st) {
 // makes those copies).  The same values as the three launches.
 // MPAS vertical solver / dynamics (physics 1 / 2): the same fusion with vert_imp's MPAS form,
 // and under the MPAS dynamics setup's theta_m_save and moist's cqu (edge blocks) too
-template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0>
+template <int LP, bool MPASV = false, bool MD = false, int KEPT = 0, bool KD = false>
 __global__ __launch_bounds__(256) void k_setup_vi(DevState S, int ncb, double dtseps, double rcv, double c2, int copies) {
-    setup_vi_body<LP, MPASV, MD, KEPT>(S, ncb, dtseps, rcv, c2, this_blk(), copies);
+    setup_vi_body<LP, MPASV, MD, KEPT, KD>(S, ncb, dtseps, rcv, c2, this_blk(), copies);
 }
 template <int LP>
 static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco, int kept,
-                              int vik) {
+                              int vik, int kd) {
     if (nco && S.physics) return hipErrorInvalidValue;  // (option accoef: reference semantics only)
     // (option vikeep: the set in scratch -- the conditions of the kept launch, in the full launch too)
     if (vik && (S.physics || S.halo || edges || !nbc || !nco)) return hipErrorInvalidValue;
+    if (kd && !kept) return hipErrorInvalidValue;  // (option a0keep: kdiff from X_kd0, a kept launch)
     if (kept) {  // (option stepkeep: w_2 and vert_imp's live columns alone, k_cols.h setup_vi_body KEPT)
         if (S.physics || S.halo || edges || !nbc || !nco) return hipErrorInvalidValue;
         const int nb = col_blocks<LP>(S, KC);
-        const double rcv = kRgas / (kCp - kRgas);
-        if (nb && vik) k_setup_vi<LP, false, false, 2><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), rcv, kCp * rcv, 14);
-        else if (nb) k_setup_vi<LP, false, false, 1><<<nb, 256, 0, st>>>(S, nb, vi_dtseps(dts), rcv, kCp * rcv, 6);
+        const double rcv = kRgas / (kCp - kRgas), dtseps = vi_dtseps(dts), c2 = kCp * rcv;
+        if (!nb) return hipGetLastError();
+        if (vik && kd) k_setup_vi<LP, false, false, 2, true><<<nb, 256, 0, st>>>(S, nb, dtseps, rcv, c2, 14);
+        else if (vik) k_setup_vi<LP, false, false, 2><<<nb, 256, 0, st>>>(S, nb, dtseps, rcv, c2, 14);
+        else if (kd) k_setup_vi<LP, false, false, 1, true><<<nb, 256, 0, st>>>(S, nb, dtseps, rcv, c2, 6);
+        else k_setup_vi<LP, false, false, 1><<<nb, 256, 0, st>>>(S, nb, dtseps, rcv, c2, 6);
         return hipGetLastError();
     }
     double dtseps = vi_dtseps(dts);
@@ -201,8 +205,8 @@ static hipError_t setup_vi_lp(const DevState& S, hipStream_t st, double dts, boo
     return hipGetLastError();
 }
 hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges, int nbc, int nco,
-                                       int kept, int vik) {
-    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco, kept, vik);
+                                       int kept, int vik, int kd) {
+    MPAS_LP_DISPATCH(S.LP, setup_vi_lp, S, st, dts, edges, nbc, nco, kept, vik, kd);
 }
 
 // one cell column copied to another at every level but L, the padding levels included (zeros in both): option
@@ -480,9 +484,25 @@ __global__ __launch_bounds__(256) void k_finish64(DevState S, int substep, int s
     finish64_body(S, substep, split, inv_split, q, blockIdx.y == 1, (int)blockIdx.x, (int)gridDim.x, norz);
 }
 
-hipError_t launch_substep_finish(const DevState& S, hipStream_t st, int substep, int split, int norz) {
+// the cell part alone (atm_srk3 option a0keep, a kept step: the edge part's ruAvg_split = ruAvg is the identity)
+__global__ __launch_bounds__(256) void k_finish64_cells(DevState S, int substep, int split, double inv_split, Pair64 q,
+                                                        int norz) {
+    finish64_part<true>(S, substep, split, inv_split, q, (int)blockIdx.x, (int)gridDim.x, norz);
+}
+
+hipError_t launch_substep_finish(const DevState& S, hipStream_t st, int substep, int split, int norz, int cells_only) {
     double inv = 1.0 / (double)split;
     if (norz && (S.physics || substep != split || S.LP != 64)) return hipErrorInvalidValue;
+    if (cells_only) {  // (the averages and, without norz, rho_zz: what the cell part writes at substep = split = 1)
+        if (S.physics || S.halo || substep != 1 || split != 1) return hipErrorInvalidValue;
+        if (S.LP == 64) {
+            const int gx = (stream_grid((size_t)S.nCO * 32) + 3) / 4;
+            k_finish64_cells<<<gx, 256, 0, st>>>(S, substep, split, inv, Pair64(S.L), norz);
+        } else {
+            k_finish_cells<<<stream_grid((size_t)S.nCO * S.LP), 256, 0, st>>>(S, substep, split, inv);
+        }
+        return hipGetLastError();
+    }
     if (S.LP == 64) {
         const int gx = (stream_grid((size_t)S.nEO * 32) + 3) / 4;
         k_finish64<<<dim3(gx, 2), 256, 0, st>>>(S, substep, split, inv, Pair64(S.L), norz);

@@ -69,6 +69,7 @@ const FieldInfo kFields[X_COUNT] = {
     {"a0", K_C3, 1, D_M, 0, 0},
     {"b0", K_C3, 1, D_M, 0, 0},
     {"c0", K_C3, 1, D_M, 0, 0},
+    {"kd0", K_C3, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -163,6 +164,14 @@ struct mpas_ctx {
     // generation, so the fields keep stage 1's; at keep_gen >= 1 both launches form alpha_tri / gamma_tri alone
     // from the stored a, b, c.  Invalidation is keep_gen's: a full step rewrites every one of them first
     int vikeep = 1;
+    // option "a0keep" (where stepkeep is active): everything stage 0's dyn_tend kernel A stores --
+    // tend_rho, dpdz, the w scratch X_wc, setup's copies ru_save / u_2 -- is a function of fields no task of the
+    // step writes, but kdiff, which reads v: stage 2 of a full step leaves another v than the one its own stage 0
+    // read.  A full step therefore ends with one launch that forms the next step's kdiff into X_kd0; a step at
+    // keep_gen >= 1 copies it into kdiff in its setup launch, runs stage 0's dyn_tend without A (B stays the
+    // instance that loads neither u nor ru) and the finish without its edge part (ruAvg has no writer, so
+    // ruAvg_split = ruAvg is the identity).  Invalidation is keep_gen's
+    int a0keep = 1;
     int keep_gen = 0;
     double keep_dt = 0.0;
     int keep_schedule = -1;
@@ -1113,6 +1122,10 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
     double dts_vi = 0.0;
     // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
     const bool vik = c->vikeep && stepkeep_active(c, dt, schedule);
+    // option a0keep: a full step leaves the next step's kdiff in X_kd0; a kept step takes it from there and runs
+    // neither stage 0's A nor the finish's edge part (stepkeep_active's step is the one whose stage 0 takes the
+    // form with setup's copies in A: fusecopy, ntu, defer4, horiz_mixing 0, undecomposed, no etile)
+    const bool a0k = c->a0keep && stepkeep_active(c, dt, schedule);
     bool flux_done = false;  // (option smlsum: the step's flux sum, beside setup and A on small grids)
     // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
     // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
@@ -1139,7 +1152,7 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
                           : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
                  [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0,
-                                                           vik ? 1 : 0); });
+                                                           vik ? 1 : 0, a0k && gen >= 1 ? 1 : 0); });
         dts_vi = rk_sub_timestep[0];
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
@@ -1181,11 +1194,14 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         // option stepkeep, any kept step: stage 2's A (rk_step > 0: h_divergence alone, from ru and the mesh --
         // no task of the step writes ru) stored the same bits in the full step; B reads them
         if (gen >= 1 && rk_step == 2) a.skipA = 1;
+        // option a0keep, any kept step: stage 0's A stored the same bits in the step before -- tend_rho, dpdz,
+        // X_wc, ru_save, u_2 -- and the setup launch has put the step's kdiff in place; B as if A had run
+        if (a0k && gen >= 1 && rk_step == 0) a.keptA = 1;
         // timing key: the variant's read / write set (bench.py parses the tags)
         const std::string dname = std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") +
                                   (a.cp ? "+copy" : "") + (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") +
                                   (a.store_v ? "+v" : "") + (a.rud != 0.0 ? "+ru" : "") + (a.smlE ? "+sml" : "") +
-                                  (a.skipA ? "-A" : "") + "]";
+                                  (a.skipA || a.keptA ? "-A" : "") + "]";
         if (keep2 && rk_step == 0) {
             run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
         } else {
@@ -1328,6 +1344,12 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
                      [&] { return launch_solve_diagnostics(S, st, 0, rk_step, live ? 7 : 3, nv); });
         }
     }
+    // option a0keep, a full step that leaves generation 1: the kdiff stage 0's A of the next step would store --
+    // from u and the v stage 2 has just left (its B, or solve_diagnostics) -- into X_kd0; the field keeps this
+    // step's.  Kernel A itself, on a state whose kdiff slot points at the scratch column; its other stores write
+    // the bytes they hold.  (Not a dyn_tend row: the step's three stay three)
+    if (a0k && gen == 0)
+        run_task(c, "a0keep_kdiff", [&] { return launch_dyn_A_kdiff(S, st, stage_args(0), X_kd0); });
     if (c->transport == 2) {
         // MPAS's RK3 transport (dynamics and transport split): every stage from scalars_old with the
         // step's ruAvg / wwAvg / rho_zz_old_split, its high-order fluxes from the stage before
@@ -1344,9 +1366,11 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         });
     if (S.physics == 2)  // the MPAS dynamics: cell-centre winds for the next step's curvature
         run_task(c, "mpas_reconstruct_2d", [&] { return launch_reconstruct_2d(S, st, 1); });  // (:487, commented)
+    // (option a0keep, a kept step: no physics 0 task writes ruAvg, so the edge part's ruAvg_split = ruAvg stored
+    // the same bytes in the step before -- the cell part alone)
     if (!(hf && fuse && S.LP == 64 && !c->transport))  // (else it ran beside solve_diagnostics' edges)
         run_task(c, norz ? "atm_rk_dynamics_substep_finish[-rz]" : "atm_rk_dynamics_substep_finish",
-                 [&] { return launch_substep_finish(S, st, 1, dynamics_split, norz ? 1 : 0); });
+                 [&] { return launch_substep_finish(S, st, 1, dynamics_split, norz ? 1 : 0, a0k && gen >= 1 ? 1 : 0); });
     fb.finish();
     // :492 summarize_timestep(cr, er, false, false, false) (constants.rg:67-69): prints only
 }
@@ -1658,6 +1682,9 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         } else if (name && std::strcmp(name, "vikeep") == 0) {
             if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "vikeep must be 0 or 1"};
             c->vikeep = (int)value;
+        } else if (name && std::strcmp(name, "a0keep") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "a0keep must be 0 or 1"};
+            c->a0keep = (int)value;
         }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
@@ -1842,6 +1869,7 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "smlkeep") == 0) *value = c->smlkeep;
         else if (name && std::strcmp(name, "stepkeep") == 0) *value = c->stepkeep;
         else if (name && std::strcmp(name, "vikeep") == 0) *value = c->vikeep;
+        else if (name && std::strcmp(name, "a0keep") == 0) *value = c->a0keep;
         else if (name && std::strcmp(name, "stepkeep_gen") == 0) *value = c->keep_gen;  // (read-only)
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;

@@ -115,6 +115,8 @@ enum FieldId {
     X_a0,       // a_tri, b_tri, c_tri as computed (used at 0 < k < L): the kept setup launch forms
     X_b0,       // alpha_tri and gamma_tri from them and the previous gamma_tri                             C3
     X_c0,
+    X_kd0,      // option a0keep: the kdiff stage 0's dyn_tend A of the next step would store (u, and the v the
+                // step leaves), formed at the end of a full step; the kept setup launch copies it to kdiff    C3
     X_COUNT
 };
 
@@ -237,6 +239,10 @@ struct DynTendArgs {
     // option "vdyn" (atm_srk3 stage 2, reference semantics): the edge kernel also stores
     // solve_diagnostics' v (:429-437, Q23) from the edgesOnEdge u it gathers (S.eoe_same)
     int store_v = 0;
+    // option "a0keep" (atm_srk3 stage 0 of a kept step): kernel A does not run and everything it would store,
+    // setup's copies (the cpA form, which the call must be) included, is in place -- unlike skipA, the edge
+    // kernel stays the one that takes the copies as made (any other form of the call: hipErrorInvalidValue)
+    int keptA = 0;
 };
 
 enum EntityKind { KC = 0, KE = 1, KV = 2 };  // DevState::lo index
@@ -273,8 +279,10 @@ inline double vi_dtseps(double dts) { return .5 * dts * (1.0 + kEpssm); }
 // (vik, atm_srk3 option vikeep, with kept's conditions: the launch's coefficient set lives in scratch -- the full
 // launch stores cofwt / cofwz to X_cofwt0 / X_cofwz0, not the fields, and a / b / c to X_a0 / X_b0 / X_c0;
 // the kept launch loads w, those three and gamma_tri and stores w_2, alpha_tri and gamma_tri alone)
+// (kd, atm_srk3 option a0keep, a kept launch: also kdiff = X_kd0, the column the last full step's last launch
+// formed for this step's stage 0 -- every position A would store, level L from kdiff's keep tail)
 hipError_t launch_setup_moist_vert_imp(const DevState& S, hipStream_t st, double dts, bool edges = true, int nbc = 0,
-                                       int nco = 0, int kept = 0, int vik = 0);
+                                       int nco = 0, int kept = 0, int vik = 0, int kd = 0);
 // atm_srk3 option vikeep, a kept step's stage-1 vert_imp (reference semantics, undecomposed): a_tri, b_tri and
 // c_tri hold this call's values from the last full step -- alpha_tri, gamma_tri and cofrz alone
 hipError_t launch_vert_imp_kept(const DevState& S, hipStream_t st, double dts);
@@ -291,6 +299,11 @@ hipError_t launch_hf_solve_e_dyn_A(const DevState& S, hipStream_t st, const DynT
 hipError_t launch_hf_setup_dyn_A(const DevState& S, hipStream_t st, const DynTendArgs& stage0, double dts, int edges,
                                  int flux = 0);
 hipError_t launch_dyn_tend(const DevState& S, hipStream_t st, const DynTendArgs& a);
+// atm_srk3 option a0keep (reference semantics, undecomposed): the rk_step 0 kernel A of stage0's call alone, with
+// its kdiff stored to the cell scratch column `to` instead of the field (every position of the column as the
+// field would hold it but level L, which takes the scratch column's own tail) -- its other stores, tend_rho, dpdz
+// and the w scratch, write the bytes a call on the same state has left
+hipError_t launch_dyn_A_kdiff(const DevState& S, hipStream_t st, const DynTendArgs& stage0, int to);
 // exact = 0 (reference semantics): the slope-flux terms summed, then subtracted (k_sml_flux's order)
 hipError_t launch_set_smlstep(const DevState& S, hipStream_t st, int exact);
 // mode (reference semantics, no halo; atm_srk3 with option "fusedamp"): 0 plain, 1 also
@@ -332,7 +345,10 @@ hipError_t launch_hf_solve_e_vert_imp(const DevState& S, hipStream_t st, double 
 hipError_t launch_solve_diagnostics(const DevState& S, hipStream_t st, int hollingsworth, int rk_step, int parts = 3,
                                     int no_v = 0);
 // (norz: atm_srk3, reference semantics, LP = 64 -- rho_zz = rho_zz_old_split is the identity there, not made)
-hipError_t launch_substep_finish(const DevState& S, hipStream_t st, int substep, int split, int norz = 0);
+// (cells_only: atm_srk3 option a0keep, a kept step, substep = split = 1, undecomposed -- ruAvg_split = ruAvg is
+// the identity there: the cell part alone, on a grid sized for the cells)
+hipError_t launch_substep_finish(const DevState& S, hipStream_t st, int substep, int split, int norz = 0,
+                                 int cells_only = 0);
 hipError_t launch_fill_synthetic(const DevState& S, hipStream_t st, uint64_t seed);
 // keep tails (below): set both tails of field f from the field; compare one tail (level 0 or
 // L) with the field on the owned entities, *flag = 2 f + lev0 + 1 on a mismatch

@@ -264,6 +264,11 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
     if task in ("stepkeep_restore_w", "stepkeep_save_w"):  # option stepkeep = 2 (no reference task)
         # one cell column read, one written: w from (to) the scratch copy of the w stage 0's dyn_tend leaves
         return ["w"], ["w"]
+    if task == "a0keep_kdiff":  # option a0keep (no reference task): the last launch of a full step
+        # the next step's Smagorinsky kdiff, from u and the v stage 2 left, into a scratch column (credited as
+        # kdiff).  The launch is dyn_tend's rk_step 0 kernel A whole; its other stores rewrite the bytes they
+        # hold and take no credit, nor do the arrays only they read
+        return ["u", "v", "defc_a", "defc_b", "nEdgesOnCell", "edgesOnCell"], ["kdiff"]
     raise KeyError(task)
 
 
