@@ -188,6 +188,15 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * atm_rk_dynamics_substep_finish without its edge part (ruAvg has no writer, so ruAvg_split = ruAvg is in
  * place).  Every field bit-identical; 0: every one of those launches in every step.  Any other value:
  * MPAS_EINVAL.
+ * "dynkeep" = 1 (default; speed only; exactly where "a0keep" is active and "stepkeep" is 1): what the dyn_tend
+ * calls of a step at "stepkeep_gen" >= 1 still form -- stage 0's edge, vertex and cell kernels, every stage's
+ * last cell kernel -- is a function of fields no task of the step writes.  Such a step launches guarded
+ * instances of those kernels, which load a flag in device memory: the first such step after a full one runs
+ * them as before and also leaves tend_u_euler (before the deferred del4) and each stage's w in scratch columns;
+ * the later ones copy those columns back and form nothing else.  The launches, the timing keys and the captured
+ * graph are the same for both.  Read-only "dynkeep_fresh": the flag (1: the columns hold the running sequence's
+ * values; a full step clears it).  Every field bit-identical; 0: the plain kernels.  Any other value:
+ * MPAS_EINVAL.
  * "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of

@@ -294,13 +294,25 @@ __global__ __launch_bounds__(256) void k_dyn_cp_orph(DevState S) {
 // setup's copies
 // NCP (a.cpA: rk_step 0, NOF and NTU): A has made setup's copies (dyn_A_body CPA); nothing else here reads u or
 // ru at the edge, so neither column is loaded
-template <int LP, bool RK0, bool MD, bool HF, bool DIN = false, bool NOF = false, bool NTU = false, bool NCP = false>
+// DK (atm_srk3 option "dynkeep", stage 0 of a kept step; the NCP fast-path form with defer4 out): everything the
+// kernel stores is a function of fields no task of the step writes, but stage 2's edge kernel adds the deferred
+// del4 to tend_u_euler in place.  X_dkf 0: the kernel as without DK, its tend_u_euler also stored to X_tue0 (the
+// same lanes and padding); 1: tend_u_euler = X_tue0 at every level but L, nothing else -- delsq_u is in place
+template <int LP, bool RK0, bool MD, bool HF, bool DIN = false, bool NOF = false, bool NTU = false, bool NCP = false,
+          bool DK = false>
 __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState S, DynK a) {
     static_assert(!NTU || !MD, "the dead tend_u: reference semantics");
     static_assert(!NCP || (RK0 && NOF && NTU), "u and ru dead at the edge: no tend_u, no flux, no rk > 0 perturbation flux");
+    static_assert(!DK || (NCP && HF), "the kept tend_u_euler: stage 0 of a kept step, fast path");
     ColMap<LP> m(S, KE);
     const int L = S.L, k = m.k, e = m.ent;
     if (e >= S.nEO) return;
+    if constexpr (DK) {
+        if (dk_fresh(S)) {
+            if (k != L) colk(fw(S, F_tend_u_euler), e) = colk(fd(S, X_tue0), e);
+            return;
+        }
+    }
     const size_t p = (size_t)e * LP + lpos(LP, k);
     constexpr bool rk0 = RK0;
     const bool live = k <= L;
@@ -629,6 +641,9 @@ __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState
             if (a.d4o) {  // (defer4: D runs in the next call's B; this tend_u is dead)
                 if constexpr (NOF) put2<LP>(tueo, e, fw(S, F_delsq_u), e, k, PADW(tue), dsq, k != L, k != L);
                 else put2<LP>(Fo, e, tueo, e, k, Hv, PADW(tue), true, k != L);
+                if constexpr (DK) {
+                    if (k != L) colk(fw(S, X_tue0), e) = PADW(tue);
+                }
                 if (!NOF && k != L) colk(fw(S, F_delsq_u), e) = dsq;
             } else {
                 if constexpr (NOF) {
@@ -902,8 +917,13 @@ __global__ __launch_bounds__(256) void k_dyn_C(DevState S, DynK a) {
 }
 // both parts in one grid, the vertex and the cell blocks interleaved in proportion
 // (vc_block, option vcmix) so that the delsq_u columns both gather are fetched into L2 once
-template <int LP, bool SELF, int VE>
+// DK (atm_srk3 option "dynkeep", stage 0 of a kept step): X_dkf 1 -- every output holds these bits already (the
+// inputs are fields no task of the step writes, and only E, guarded alike, rewrites two of the outputs): nothing
+template <int LP, bool SELF, int VE, bool DK = false>
 __global__ __launch_bounds__(256) void k_dyn_C12(DevState S, DynK a, int nv) {
+    if constexpr (DK) {
+        if (dk_fresh(S)) return;
+    }
     int bi;
     if (vc_block(S, xcd_block(S.xcd), nv, bi)) dyn_C_body<LP, SELF, VE, 1>(S, a, bi);
     else dyn_C_body<LP, SELF, VE, 2>(S, a, bi);
@@ -964,10 +984,17 @@ struct EtTile {
 // SMLF (option msml, the MPAS dynamics): the stage's atm_set_smlstep_pert_variables_work applied to the
 // tend_w formed here (k_set_smlstep's MD form: the same loads and the same order of operations, from the
 // value it would read back), so its launch and the tend_w round trip go
+// DK (atm_srk3 option "dynkeep", a kept step's stale pass; the fresh one is dyn_E_body's): the w stored here
+// also goes to the stage's scratch column (dk_wcol), every position as the field takes it
+template <bool RK0, bool NTH>
+constexpr int dk_wcol() { return RK0 ? X_w0 : NTH ? X_w1 : X_w2; }  // (stages 0, 1, 2 of atm_srk3: one E form each)
+template <bool RK0, bool NTH>
+constexpr bool dk_in_E() { return !RK0 && NTH; }  // (the stage whose E stores the copy itself: dyn_E_body)
 template <int LP, bool RK0, bool SELF, bool MD, bool HF, bool TILE = false, int ETM = 0, bool NTH = false,
-          bool SMLF = false>
+          bool SMLF = false, bool DK = false>
 __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int c, int k, EtTile tl = {}) {
     static_assert(!NTH || (!MD && !TILE), "the dead theta tendency: reference semantics, untiled");
+    static_assert(!DK || (HF && !MD && !TILE && !SMLF), "the kept w: the fast path, reference semantics, untiled");
     static_assert(!TILE || (LP == 64 && !MD), "the tiled E: LP = 64, reference semantics");
     const int L = S.L;
     const size_t p = (size_t)c * LP + lpos(LP, k);
@@ -1309,6 +1336,7 @@ __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int
         }
         if constexpr (HF) {
             colk(fw(S, F_w), c) = KEEPW(w, kl_w);
+            if constexpr (DK) colk(fw(S, dk_wcol<RK0, NTH>()), c) = KEEPW(w, kl_w);
             if (rk0)
                 put2f<LP>(fw(S, F_tend_w_euler), c, fw(S, F_tend_theta_euler), c, k, KEEPW(twe, kl_twe),
                          KEEPW(tte, kl_tte));
@@ -1383,6 +1411,7 @@ __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int
         if (!MD)
             put2f<LP>(fw(S, F_w), c, fw(S, F_tend_rtheta_adv), c, k, KEEPW(w, kl_w),
                      KEEPW(tend_theta, kl_tra));
+        if constexpr (DK) colk(fw(S, dk_wcol<RK0, NTH>()), c) = KEEPW(w, kl_w);
         tend_theta += rho_zz * rt_diab;
         tend_theta += tte + trp;
         put2f<LP>(fw(S, F_rthdynten), c, fw(S, F_tend_theta), c, k, KEEPW(rth, kl_rth), KEEPW(tend_theta, kl_tt));
@@ -1404,11 +1433,31 @@ __device__ __forceinline__ void dyn_E_cell(const DevState& S, const DynK& a, int
     if (rk0) colk(fw(S, F_tend_theta_euler), c) = PADW(tte);
 }
 
-template <int LP, bool RK0, bool SELF, bool MD, bool HF, bool NTH = false, bool SMLF = false>
+// DK, X_dkf 1: everything E stores is in place from the step before -- functions of fields no task of the step
+// writes -- but w, which the acoustic launches and the next stage have rewritten: w = the stage's scratch column
+// below level L, the padding as E stores it (zeros there), level L -- which evolves -- untouched.  No other store
+template <int LP, bool RK0, bool SELF, bool MD, bool HF, bool NTH = false, bool SMLF = false, bool DK = false>
 __device__ __forceinline__ void dyn_E_body(const DevState& S, const DynK& a, Blk bk) {
     ColMap<LP> m(S, KC, bk);
     if (m.ent >= S.nCO) return;
-    dyn_E_cell<LP, RK0, SELF, MD, HF, false, 0, NTH, SMLF>(S, a, m.ent, m.k);
+    if constexpr (DK) {
+        if (dk_fresh(S)) {
+            const int k = m.k;
+            if (k != S.L) colk(fw(S, F_w), m.ent) = colk(fd(S, dk_wcol<RK0, NTH>()), m.ent);
+            return;
+        }
+    }
+    // (the stale pass's copy of w: stored by stage 1's E itself; stage 0's and stage 2's would each lose a wave of
+    // occupancy to the extra store -- 73 / 76 VGPRs against 69 / 68 at LP 64 -- so k_dk_save makes it after them)
+    dyn_E_cell<LP, RK0, SELF, MD, HF, false, 0, NTH, SMLF, DK && dk_in_E<RK0, NTH>()>(S, a, m.ent, m.k);
+}
+// the copy of w for the stages whose E does not store it: X_dkf 0 -- cell column `to` = w, every position; 1: nothing
+__global__ __launch_bounds__(256) void k_dk_save(DevState S, int to) {
+    if (dk_fresh(S)) return;
+    const size_t n = (size_t)S.nCO * S.LP / 2;  // (LP is even: whole double2s)
+    const double2* s = (const double2*)fd(S, F_w);
+    double2* d = (double2*)fw(S, to);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s[i];
 }
 
 // option "etile" (reference semantics, LP = 64): E over the tiles of TrTiles (mpas_dev.h; the
@@ -1533,9 +1582,9 @@ __global__ __launch_bounds__(NT, ETM == 2 && !RK0 ? 5 : 4) void k_dyn_Et(DevStat
 
 // (rk_step > 0, reference semantics, LP = 64: 4 waves per SIMD, as before E formed wc itself;
 // at LP < 64 that cap spilled 10-22 VGPRs)
-template <int LP, bool RK0, bool SELF, bool MD, bool HF, bool NTH = false, bool SMLF = false>
+template <int LP, bool RK0, bool SELF, bool MD, bool HF, bool NTH = false, bool SMLF = false, bool DK = false>
 __global__ __launch_bounds__(256, LP == 64 && !RK0 && !MD ? 4 : 1) void k_dyn_E(DevState S, DynK a) {
-    dyn_E_body<LP, RK0, SELF, MD, HF, NTH, SMLF>(S, a, this_blk());
+    dyn_E_body<LP, RK0, SELF, MD, HF, NTH, SMLF, DK>(S, a, this_blk());
 }
 // D and E of rk_step 0 in one grid (option "hfuse": neither reads what the other writes)
 template <int LP, bool SELF, bool MD, bool HF>
@@ -1612,6 +1661,11 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     // (in.keptA, atm_srk3 option a0keep: A's stores of an earlier call of this form are in place, the copies
     // included -- no A, no k_dyn_cp_orph, and B the NCP instance as if A had just run; only that form)
     if (in.keptA && !a.cpA) return hipErrorInvalidValue;
+    // (in.dynkeep, atm_srk3 option dynkeep: the guarded instances of this call's B, C and E -- k_dyn_B DK,
+    // k_dyn_C12 DK, dyn_E_body DK -- which exist for a kept step's forms alone)
+    const bool dk = in.dynkeep != 0;
+    if (dk && (MD || !hf || et || S.halo || in.smlE || in.hfuse || (rk0 && !(in.keptA && a.d4o && ntu && nth))))
+        return hipErrorInvalidValue;
     auto kB = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KE);
         if (!nb) return;
@@ -1636,6 +1690,12 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
                 auto go4 = [&](auto R, auto H, auto Di) {
                     if constexpr (decltype(R)::value && !decltype(Di)::value) {
                         if (a.cpA) {  // (the copies made by A: NCP)
+                            if constexpr (decltype(H)::value) {
+                                if (dk) {
+                                    k_dyn_B<LP, true, false, true, false, true, true, true, true><<<nb, 256, 0, st>>>(X, a);
+                                    return;
+                                }
+                            }
                             k_dyn_B<LP, true, false, decltype(H)::value, false, true, true, true><<<nb, 256, 0, st>>>(X, a);
                             return;
                         }
@@ -1677,6 +1737,13 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
             constexpr int VE = LP == 64 ? decltype(ve)::value : 1;
             const int nv = del4 ? col_blocks_n<LP, VE>(X, KV) : 0, nc = col_blocks<LP>(X, KC);
             if (nv && nc) {
+                if constexpr (!MD) {
+                    if (dk) {  // (a kept step's C is always this grid: del4 on, cells and vertices)
+                        if (X.selfc) k_dyn_C12<LP, true, VE, true><<<nv + nc, 256, 0, st>>>(X, a, nv);
+                        else k_dyn_C12<LP, false, VE, true><<<nv + nc, 256, 0, st>>>(X, a, nv);
+                        return;
+                    }
+                }
                 if (X.selfc) k_dyn_C12<LP, true, VE><<<nv + nc, 256, 0, st>>>(X, a, nv);
                 else k_dyn_C12<LP, false, VE><<<nv + nc, 256, 0, st>>>(X, a, nv);
                 return;
@@ -1732,6 +1799,22 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
             }
         }
         if constexpr (!MD) {
+            if (dk) {  // (hf holds; stage 0: RK0 NTH, stage 1: NTH, stage 2: neither -- dk_wcol's three forms)
+                const int ng = stream_grid_((size_t)X.nCO * LP / 2);  // (k_dk_save, where E leaves the copy to it)
+                if (rk0 && nth) {
+                    if (X.selfc) k_dyn_E<LP, true, true, false, true, true, false, true><<<nb, 256, 0, st>>>(X, a);
+                    else k_dyn_E<LP, true, false, false, true, true, false, true><<<nb, 256, 0, st>>>(X, a);
+                    k_dk_save<<<ng, 256, 0, st>>>(X, dk_wcol<true, true>());
+                } else if (nth) {
+                    if (X.selfc) k_dyn_E<LP, false, true, false, true, true, false, true><<<nb, 256, 0, st>>>(X, a);
+                    else k_dyn_E<LP, false, false, false, true, true, false, true><<<nb, 256, 0, st>>>(X, a);
+                } else {
+                    if (X.selfc) k_dyn_E<LP, false, true, false, true, false, false, true><<<nb, 256, 0, st>>>(X, a);
+                    else k_dyn_E<LP, false, false, false, true, false, false, true><<<nb, 256, 0, st>>>(X, a);
+                    k_dk_save<<<ng, 256, 0, st>>>(X, dk_wcol<false, false>());
+                }
+                return;
+            }
             if (nth) {  // (k_dyn_E NTH: the theta tendencies dead in this call)
                 auto go = [&](auto hfc) {
                     constexpr bool H = decltype(hfc)::value;
@@ -1853,6 +1936,15 @@ static hipError_t dyn_lp(const DevState& S, hipStream_t st, const DynTendArgs& i
 }
 hipError_t launch_dyn_tend(const DevState& S, hipStream_t st, const DynTendArgs& in) {
     MPAS_LP_DISPATCH(S.LP, dyn_lp, S, st, in);
+}
+
+// option "dynkeep": the flag the guarded instances above load (X_dkf), stored by one lane between their launches
+__global__ void k_dk_flag(int* flag, int fresh) {
+    if (threadIdx.x == 0) *flag = fresh;
+}
+hipError_t launch_dk_flag(const DevState& S, hipStream_t st, int fresh) {
+    k_dk_flag<<<1, 64, 0, st>>>((int*)S.f[X_dkf], fresh ? 1 : 0);
+    return hipGetLastError();
 }
 
 // option "a0keep" (atm_srk3, reference semantics, undecomposed): the last launch of a full step forms the

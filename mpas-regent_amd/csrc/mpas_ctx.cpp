@@ -70,6 +70,10 @@ const FieldInfo kFields[X_COUNT] = {
     {"b0", K_C3, 1, D_M, 0, 0},
     {"c0", K_C3, 1, D_M, 0, 0},
     {"kd0", K_C3, 1, D_M, 0, 0},
+    {"tue0", K_E3, 1, D_M, 0, 0},
+    {"w1", K_C3, 1, D_M, 0, 0},
+    {"w2", K_C3, 1, D_M, 0, 0},
+    {"dkf", K_ZV, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -172,6 +176,14 @@ struct mpas_ctx {
     // instance that loads neither u nor ru) and the finish without its edge part (ruAvg has no writer, so
     // ruAvg_split = ruAvg is the identity).  Invalidation is keep_gen's
     int a0keep = 1;
+    // option "dynkeep" (where a0keep is active and stepkeep is 1): what a kept step's dyn_tend
+    // still forms from fields no task of the step writes -- stage 0's B, C and E, stage 1's and 2's E -- is
+    // formed by the first kept step after a full one alone, which also leaves the columns the step rewrites
+    // (tend_u_euler before its del4, each stage's w) in X_tue0 / X_w0..2.  The later kept steps launch the same
+    // kernels, which copy those columns back and return: the decision is a device flag (X_dkf) the guarded
+    // instances load, cleared by every full step and set by every kept one, so one captured graph serves both.
+    // Invalidation is keep_gen's: an outside call leads to a full step, which clears the flag first
+    int dynkeep = 1;
     int keep_gen = 0;
     double keep_dt = 0.0;
     int keep_schedule = -1;
@@ -1126,6 +1138,10 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
     // neither stage 0's A nor the finish's edge part (stepkeep_active's step is the one whose stage 0 takes the
     // form with setup's copies in A: fusecopy, ntu, defer4, horiz_mixing 0, undecomposed, no etile)
     const bool a0k = c->a0keep && stepkeep_active(c, dt, schedule);
+    // option dynkeep: a kept step launches the guarded instances of stage 0's B, C and E and of stage 1's and 2's
+    // E, which decide on X_dkf; a full step clears the flag (in its setup task), a kept one sets it after stage
+    // 2's E (in that dyn_tend task): no timing key of its own.  (stepkeep = 2 skips those launches on the host)
+    const bool dk = c->dynkeep && a0k && c->stepkeep == 1;
     bool flux_done = false;  // (option smlsum: the step's flux sum, beside setup and A on small grids)
     // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
     // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
@@ -1151,8 +1167,14 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         const bool nbc = c->ntu == 1 || c->ntu == 2;
         run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
                           : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
-                 [&] { return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0,
-                                                           vik ? 1 : 0, a0k && gen >= 1 ? 1 : 0); });
+                 [&] {
+                     if (dk && gen == 0) {  // (the columns of option dynkeep are stale from here on)
+                         const hipError_t e = launch_dk_flag(S, st, 0);
+                         if (e != hipSuccess) return e;
+                     }
+                     return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0,
+                                                        vik ? 1 : 0, a0k && gen >= 1 ? 1 : 0);
+                 });
         dts_vi = rk_sub_timestep[0];
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
@@ -1197,6 +1219,10 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         // option a0keep, any kept step: stage 0's A stored the same bits in the step before -- tend_rho, dpdz,
         // X_wc, ru_save, u_2 -- and the setup launch has put the step's kdiff in place; B as if A had run
         if (a0k && gen >= 1 && rk_step == 0) a.keptA = 1;
+        // option dynkeep, any kept step: the guarded instances -- the first kept step after a full one runs them as
+        // the plain ones and fills X_tue0 / X_w0..2, the later ones copy those back (the same launches: one graph)
+        const bool dkept = dk && gen >= 1;
+        if (dkept) a.dynkeep = rk_step + 1;
         // timing key: the variant's read / write set (bench.py parses the tags)
         const std::string dname = std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") +
                                   (a.cp ? "+copy" : "") + (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") +
@@ -1205,7 +1231,11 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
         if (keep2 && rk_step == 0) {
             run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
         } else {
-            run_task(c, dname.c_str(), [&] { return launch_dyn_tend(S, st, a); });
+            run_task(c, dname.c_str(), [&] {
+                const hipError_t e = launch_dyn_tend(S, st, a);
+                // (option dynkeep: the step's last guarded launch is behind -- the columns hold this step's values)
+                return (dkept && rk_step == 2 && e == hipSuccess) ? launch_dk_flag(S, st, 1) : e;
+            });
             if (gen == 1 && c->stepkeep == 2 && rk_step == 0)  // (the copy a generation-2 step restores)
                 run_task(c, "stepkeep_save_w", [&] { return launch_cell_col_copy(S, st, F_w, X_w0); });
         }
@@ -1685,6 +1715,9 @@ int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
         } else if (name && std::strcmp(name, "a0keep") == 0) {
             if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "a0keep must be 0 or 1"};
             c->a0keep = (int)value;
+        } else if (name && std::strcmp(name, "dynkeep") == 0) {
+            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "dynkeep must be 0 or 1"};
+            c->dynkeep = (int)value;
         }
         else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
         else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
@@ -1871,6 +1904,14 @@ int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
         else if (name && std::strcmp(name, "vikeep") == 0) *value = c->vikeep;
         else if (name && std::strcmp(name, "a0keep") == 0) *value = c->a0keep;
         else if (name && std::strcmp(name, "stepkeep_gen") == 0) *value = c->keep_gen;  // (read-only)
+        else if (name && std::strcmp(name, "dynkeep") == 0) *value = c->dynkeep;
+        else if (name && std::strcmp(name, "dynkeep_fresh") == 0) {  // (read-only: the device flag X_dkf)
+            int fresh = 0;
+            hipcheck(hipSetDevice(c->device), "hipSetDevice");
+            hipcheck(hipMemcpyAsync(&fresh, c->S.f[X_dkf], sizeof(fresh), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+            hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+            *value = fresh;
+        }
         else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
         else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;
         else if (name && std::strcmp(name, "vdyn") == 0) *value = c->vdyn;

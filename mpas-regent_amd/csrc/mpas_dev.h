@@ -117,6 +117,14 @@ enum FieldId {
     X_c0,
     X_kd0,      // option a0keep: the kdiff stage 0's dyn_tend A of the next step would store (u, and the v the
                 // step leaves), formed at the end of a full step; the kept setup launch copies it to kdiff    C3
+    // option dynkeep: what stage 0's B and the three stages' E of a kept step store, functions of fields no task
+    // of the step writes -- filled by the first kept step after a full one (X_dkf 0), read by the later ones
+    // (X_dkf 1) in place of the kernels' work; X_w0 (above) is stage 0's w
+    X_tue0,     // stage 0's tend_u_euler before the deferred del4 (stage 2's B applies it in place)               E3
+    X_w1,       // the w stage 1's and stage 2's E leave below level L (the acoustic launches and the next
+    X_w2,       // stage rewrite w in between)                                                                  C3
+    X_dkf,      // one int: 1 when the four columns above hold the running step's values (set by a kept step's
+                // last dyn_tend, cleared by a full step), else 0                                               ZV
     X_COUNT
 };
 
@@ -243,6 +251,12 @@ struct DynTendArgs {
     // setup's copies (the cpA form, which the call must be) included, is in place -- unlike skipA, the edge
     // kernel stays the one that takes the copies as made (any other form of the call: hipErrorInvalidValue)
     int keptA = 0;
+    // option "dynkeep" (atm_srk3, a kept step; the stage, 1-based): the guarded instances of the edge kernel
+    // (stage 0), C (stage 0) and E -- each loads X_dkf first; 0: the call as without the option, and its
+    // tend_u_euler / w also stored to X_tue0 / X_w0..2; 1: those columns copied back, nothing else formed.
+    // Only the forms a kept step launches (keptA at stage 0, the fast path, undecomposed): any other
+    // hipErrorInvalidValue
+    int dynkeep = 0;
 };
 
 enum EntityKind { KC = 0, KE = 1, KV = 2 };  // DevState::lo index
@@ -299,6 +313,8 @@ hipError_t launch_hf_solve_e_dyn_A(const DevState& S, hipStream_t st, const DynT
 hipError_t launch_hf_setup_dyn_A(const DevState& S, hipStream_t st, const DynTendArgs& stage0, double dts, int edges,
                                  int flux = 0);
 hipError_t launch_dyn_tend(const DevState& S, hipStream_t st, const DynTendArgs& a);
+// option dynkeep: X_dkf = fresh (0 / 1), one lane's store
+hipError_t launch_dk_flag(const DevState& S, hipStream_t st, int fresh);
 // atm_srk3 option a0keep (reference semantics, undecomposed): the rk_step 0 kernel A of stage0's call alone, with
 // its kdiff stored to the cell scratch column `to` instead of the field (every position of the column as the
 // field would hold it but level L, which takes the scratch column's own tail) -- its other stores, tend_rho, dpdz
@@ -849,6 +865,9 @@ template <class T>
 __device__ __forceinline__ T ldc(const T* p) {
     return *(const MPAS_CONST T*)(uintptr_t)p;
 }
+// option dynkeep's flag (X_dkf; written between kernels only, by k_dk_flag): one scalar load, so the branch on
+// it is wave-uniform
+__device__ __forceinline__ bool dk_fresh(const DevState& S) { return ldc(fi(S, X_dkf)) != 0; }
 
 // the first N entries of a padded mesh-data row, loaded unconditionally (every row is
 // allocated at its full width, so the entries past the list's length are in bounds).
