@@ -148,7 +148,7 @@ struct mpas_ctx {
     // the sum's inputs -- u_tend, zb_cell, zb3_cell, edgesOnCell_sign, fzm, fzp, the mesh lists, rw -- have no
     // writer among the step's tasks, so only a call from outside can change them
     bool sml_valid = false;
-    // option "stepkeep" (reference semantics, where stepkeep_active holds): no task of the step
+    // option "stepkeep" (reference semantics, where StepForm::stepkeep holds): no task of the step
     // writes u, ru, rw, rho_zz, theta_m, rho_p, rtheta_p, h, zz, exner or the base fields, so most of what a step
     // stores is what the step before stored.  keep_gen counts the steps completed since the last call from
     // outside that could have changed a field or the form of the step (0, 1, 2: sml_valid generalised; cleared
@@ -458,6 +458,15 @@ const Roctx& roctx() {
     return r;
 }
 
+// the derived mesh arrays (k_prepare), where an upload or an init task has left them stale
+void prepare_mesh(mpas_ctx* c) {
+    if (!c->dirty) return;
+    hipcheck(launch_prepare(c->S, c->stream), "prepare");
+    c->self_ok = c->S.selfc;
+    c->S.selfc = c->self_ok && c->self_on;
+    c->dirty = false;
+}
+
 template <class Fn>
 void run_task(mpas_ctx* c, const char* name, Fn&& fn) {
     const Roctx& rx = roctx();
@@ -476,12 +485,7 @@ void run_task(mpas_ctx* c, const char* name, Fn&& fn) {
         e1 = get_event(c);
         hipcheck(hipEventRecord(e0, c->stream), "hipEventRecord");
     }
-    if (c->dirty) {
-        hipcheck(launch_prepare(c->S, c->stream), "prepare");
-        c->self_ok = c->S.selfc;
-        c->S.selfc = c->self_ok && c->self_on;
-        c->dirty = false;
-    }
+    prepare_mesh(c);
     ett_ensure(c);  // (built before a capture by prepare_now)
     hipError_t e = fn();
     if (e != hipSuccess) {
@@ -908,34 +912,18 @@ void trt_ensure(mpas_ctx* c) {
     if (c->trt_dirty) trt_build(c);
 }
 
-// option hfuse (reference semantics, undecomposed); 2: only below this many owned cells
-// (a cell kernel then has fewer than ~16 wavefronts per SIMD: the launches do not fill the
-// chip and their fixed cost dominates)
-constexpr int hfuse_auto_cells = 16384;
-bool hfuse_active(const mpas_ctx* c) {
-    if (c->S.physics != 0 || c->halo) return false;
-    return c->hfuse == 1 || (c->hfuse == 2 && c->S.nCO < hfuse_auto_cells);
-}
-
 // timing keys: one Regent task, split where its read/write set (B_alg) differs by argument
 // (bench.py aggregates the variants per task)
+// (sml: option fusesml, the stage's set_smlstep run by this launch first; 2: from the step's flux sum X_smlS)
+// (damp: option fusedamp, the previous substep's damping applied by this launch)
 // (nold: a fused launch that does not store rtheta_pp_old -- every one but the step's last --
 // tagged "-old" so that bench.py credits it no rtheta_pp_old write)
-// (sml 2: set_smlstep from the step's flux sum X_smlS, "+smlS")
-const char* acoustic_name(int small_step, bool damp = false, int sml = 0, bool nold = false) {
-    if (sml == 2)
-        return damp ? (nold ? "atm_advance_acoustic_step_work[ss0+smlS+damp-old]" : "atm_advance_acoustic_step_work[ss0+smlS+damp]")
-                    : (nold ? "atm_advance_acoustic_step_work[ss0+smlS-old]" : "atm_advance_acoustic_step_work[ss0+smlS]");
-    if (sml)  // (option fusesml: the stage's set_smlstep run by this launch first)
-        return damp ? (nold ? "atm_advance_acoustic_step_work[ss0+sml+damp-old]" : "atm_advance_acoustic_step_work[ss0+sml+damp]")
-                    : (nold ? "atm_advance_acoustic_step_work[ss0+sml-old]" : "atm_advance_acoustic_step_work[ss0+sml]");
-    if (damp)  // (option fusedamp: the previous substep's damping applied by this launch)
-        return small_step == 0
-                   ? (nold ? "atm_advance_acoustic_step_work[ss0+damp-old]" : "atm_advance_acoustic_step_work[ss0+damp]")
-                   : (nold ? "atm_advance_acoustic_step_work[ss>0+damp-old]" : "atm_advance_acoustic_step_work[ss>0+damp]");
-    if (nold) return small_step == 0 ? "atm_advance_acoustic_step_work[ss0-old]" : "atm_advance_acoustic_step_work[ss>0-old]";
-    return small_step == 0 ? "atm_advance_acoustic_step_work[ss0]" : "atm_advance_acoustic_step_work[ss>0]";
+std::string acoustic_name(int small_step, bool damp = false, int sml = 0, bool nold = false) {
+    return std::string("atm_advance_acoustic_step_work[") + (sml == 2 ? "ss0+smlS" : sml ? "ss0+sml" : small_step == 0 ? "ss0" : "ss>0") +
+           (damp ? "+damp" : "") + (nold ? "-old" : "") + "]";
 }
+// a tag inside a key's closing bracket: tagged("task[ss0]", "-st") is "task[ss0-st]" (an empty tag: the key)
+std::string tagged(std::string key, const char* tag) { return key.insert(key.size() - 1, tag); }
 
 // the buffer pairs of the deferred damping (k_acoustic MODE 2), swapped by atm_srk3 after
 // each launch; restored on exit (the ru_p pair by a copy if a step ended on the second
@@ -985,55 +973,219 @@ void tr_rk_supported(mpas_ctx* c, const char* what) {
     if (c->trtile || c->tredge || c->S.trsu || c->S.trepw == 2)
         throw Fail{MPAS_ENOTSUP, std::string(what) + ": not with trtile, tredge, trsu or trepw = 2"};
 }
-
-// option smlkeep: the step takes X_smlS as it stands -- an undecomposed context whose step uses the sum
-// (srk3's smls: the fast path with fusedamp, fusesml and smlsum).  Decomposed contexts form it in every
-// step: skipping the kernel there would skip its exchange of u_tend too
-bool smlkeep_active(const mpas_ctx* c) {
-    return c->smlkeep && !c->halo && c->S.physics == 0 && c->fusedamp && c->fusesml && c->smlsum && !c->exact;
+// dyn_tend's timing key: the variant's read / write set (bench.py parses the tags)
+std::string dyn_tend_key(const DynTendArgs& a) {
+    return std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") + (a.cp ? "+copy" : "") +
+           (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") + (a.store_v ? "+v" : "") +
+           (a.rud != 0.0 ? "+ru" : "") + (a.smlE ? "+sml" : "") + (a.skipA || a.keptA ? "-A" : "") + "]";
 }
-// ... formed here when its inputs may have changed since the kernel last ran (mpas_ctx::sml_valid): on the
-// task stream ahead of the step and outside any capture, under the flux task's timing key.  With dd0 the
-// kernel reads nothing a step writes; without it X_Dd comes from rw alone (the setup that follows stores
-// rw_save = rw, and no task of the step writes rw), so ahead of the setup is the same computation
-void sml_ensure(mpas_ctx* c) {
-    if (!smlkeep_active(c) || c->sml_valid) return;
+
+// ---- atm_srk3 (rk_timestep.rg:361-500) --------------------------------------------------
+// StepForm: everything a step decides before its first launch, each condition once (step_form).  StepRun: what
+// changes from launch to launch.  The stage functions below read both; srk3 is their sequence.
+
+// option hfuse = 2: only below this many owned cells (a cell kernel then has fewer than ~16 wavefronts per
+// SIMD: the launches do not fill the chip and their fixed cost dominates)
+constexpr int hfuse_auto_cells = 16384;
+
+struct StepForm {
+    double dt;
+    int schedule, gen;  // gen: the kept generation the step runs at (option stepkeep; 0: every launch of the step)
+    // the reference's constants (rk_timestep.rg:378-399)
+    int dynamics_split;
+    double rk_sub_timestep[3];
+    int number_sub_steps[3];
+    int n_small[3];  // acoustic launches of each stage (Q5; the MPAS form: number_sub_steps), and of the step
+    int n_acoustic;
+    int rk_of[3];  // the rk_step argument of each stage's dyn_tend (Q4)
+    // options as the launches take them, and the switches derived from them (step_form has the reasons)
+    int physics, exact, ntu;
+    bool trfold, fcopy, fuse, sml, smls, keep, hf2, finish_fused;
+    int tme, hf, ddx, fluxf, aco;
+    bool defer4, d4_pending, mru, msml, md_fold;
+    bool early_state_dead, early_diag_dead, solve0_dead, norz;
+    bool stepkeep, vik, a0k, dk, kept, keep2;
+};
+
+StepForm step_form(const mpas_ctx* c, double dt, int schedule, int gen) {
+    const DevState& S = c->S;
+    StepForm f{dt, schedule, gen};
+    f.physics = S.physics, f.exact = c->exact, f.ntu = c->ntu;
+    // rk_timestep.rg:378-399
+    const int number_of_sub_steps = 2;
+    f.dynamics_split = 1;  // constants.rg:62
+    const double dt_dynamics = dt;
+    f.rk_sub_timestep[0] = dt_dynamics / 3;
+    f.rk_sub_timestep[1] = f.rk_sub_timestep[2] = dt_dynamics / number_of_sub_steps;
+    f.number_sub_steps[0] = (number_of_sub_steps / 2 > 1) ? number_of_sub_steps / 2 : 1;
+    f.number_sub_steps[1] = f.number_sub_steps[0];
+    f.number_sub_steps[2] = number_of_sub_steps;
+    for (int s = 0; s < 3; s++) {
+        f.n_small[s] = f.number_sub_steps[s] + (S.physics ? 0 : 1);  // Q5 (the MPAS form: n)
+        f.n_acoustic += f.n_small[s];
+        f.rk_of[s] = schedule == 0 ? (int)f.rk_sub_timestep[s] : s;  // Q4: the reference driver passes the stage's time step
+    }
+    // option trsave: scalars_save's copy folded into the transport's bounds kernel (its tables decided here:
+    // the tiled and LDS-edge forms need none of them built, su stored)
+    // (transport = 2: the separate copy -- its first stage reads scalars and scalars_old)
+    f.trfold = c->transport == 1 && c->trsave && !c->halo && !c->trtile && !c->tredge && !S.trsu;
+    // option fusecopy: ru_save / u_2 by stage 0's dyn_tend edge kernel (reads u and ru there;
+    // no task between the setup and that kernel reads ru_save or u_2, in any physics mode)
+    f.fcopy = c->fusesetup && c->fusecopy;
+    // option fusedamp (reference semantics): each damping but the step's last is applied by
+    // the next acoustic launch (k_acoustic MODE 2), the last from the div the acoustic step
+    // stored (launch_div_damping_div); the same bits as the separate task.  Decomposed (option
+    // fusedamp_halo): the div is exchanged where rtheta_pp was, the ring-1 edges stay fresh
+    f.fuse = c->fusedamp && S.physics == 0 && (!c->halo || (c->fusedamp_halo && S.ring1 && S.nERing >= S.nEO));
+    // option fusesml (with fusedamp): the stage's first acoustic launch runs set_smlstep first
+    f.sml = f.fuse && c->fusesml;
+    // option tmedge (reference semantics, undecomposed): dyn_tend's edge kernel stores
+    // theta_m(cell2) + theta_m(cell1) per edge, which the stage's acoustic substeps and the
+    // damping read instead of gathering theta_m at both cells (theta_m unchanged in between)
+    f.tme = (c->tmedge && S.physics == 0 && !c->halo) ? 1 : 0;
+    // option hfuse (reference semantics, undecomposed): neighbouring kernels that neither
+    // read what the other writes share a launch (k_solve.hip combined launches, dyn_tend's
+    // rk 0 D beside E); the same values.  2: where the grids do not fill the chip
+    f.hf = (S.physics == 0 && !c->halo && (c->hfuse == 1 || (c->hfuse == 2 && S.nCO < hfuse_auto_cells))) ? 1 : 0;
+    // hfuse with fusedamp (and the default epw, no tmedge): a stage's last acoustic launch
+    // beside its solve_diagnostics vertex / cell kernel, and the stage's edge kernel beside
+    // the next stage's dyn_tend A (k_acoustic.hip / k_dyn.hip combined launches)
+    f.hf2 = f.hf && f.fuse && !f.tme && S.epw == 2;
+    // ... and the last stage's solve_diagnostics edge kernel beside atm_rk_dynamics_substep_finish
+    f.finish_fused = f.hf && f.fuse && S.LP == 64 && !c->transport;
+    // option smlsum (fast path, with fusesml): the slope-flux sum of set_smlstep formed once per
+    // step (X_smlS); each stage's fused set_smlstep then reads one column instead of u_tend at
+    // the cell's edges and zb_cell / zb3_cell (none of them written within the step)
+    f.smls = f.fuse && c->fusesml && c->smlsum && !c->exact && S.physics == 0;
+    // option smlkeep: the step takes X_smlS as it stands -- an undecomposed context whose step uses the sum;
+    // srk3_run formed it ahead of the step where its inputs may have changed since it last did (sml_ensure) --
+    // no flux launch in the step, so none in a captured one.  Decomposed contexts form it in every step:
+    // skipping the kernel there would skip its exchange of u_tend too
+    f.keep = f.smls && c->smlkeep && !c->halo;
+    // option dd0 (reference semantics): every acoustic launch takes rw_save - rw as 0.0 (ddx 2); without it
+    // the launches of a step with smlsum read the difference from X_Dd (ddx 1), the others both columns
+    f.ddx = (c->dd0 && S.physics == 0) ? 2 : f.smls ? 1 : 0;
+    f.fluxf = f.ddx == 2 ? 2 : 1;  // (the flux body beside the setup: with X_Dd or without)
+    // option accoef (reference semantics, where nothing writes theta_m within the step): every acoustic
+    // launch forms cofwr / coftz / a_tri itself, with the dts of the setup or vert_imp launch that formed
+    // the live coefficient set (StepRun::dts_vi, recorded at each of those launches -- not the acoustic launch's own)
+    // (not with option tmedge, off by default: its launches keep loading the stored set -- the exact first
+    // launch of that form would lose a wave of occupancy to the three expressions, profiles/r08)
+    f.aco = (c->accoef && S.physics == 0 && !f.tme) ? 1 : 0;
+    // option defer4: an rk_step 0 stage followed by an rk_step > 0 one leaves its kernel D
+    // (tend_u_euler's del4 part; its tend_u is dead: the next stage rewrites it and no task
+    // in between reads it in the reference semantics) to the next stage's edge kernel
+    f.defer4 = c->defer4 && S.physics == 0;
+    // (with option ntu the deferred del4 waits for the last stage's edge kernel, stage_args)
+    f.d4_pending = (f.rk_of[0] == 0 && f.rk_of[1] != 0) || (f.rk_of[1] == 0 && f.rk_of[2] != 0);
+    // option mru (the MPAS dynamics, fast path): the kernel that forms the stage's final tend_u also
+    // stores the first acoustic substep's ru_p = dts tend_u and ruAvg = ru_p (nothing in between reads
+    // or writes them; set_smlstep reads tend_u only)
+    f.mru = c->mru && S.physics == 2 && !c->exact;
+    // option msml (the MPAS dynamics): the stage's set_smlstep (:1503-1528) applied by E to the tend_w it
+    // forms -- set_smlstep follows dyn_tend directly and reads tend_u, which B / D have finished
+    f.msml = c->msml && S.physics == 2;
+    // option mdamp (the MPAS forms): the previous substep's damping in this substep's ru_p kernel, the
+    // stage's last one in the recover edge kernel -- each read-modify-write of ru_p goes
+    f.md_fold = c->mdamp && S.physics;
+    // option ntu, the dead acoustic state of the stages before the last (ntu 1 and 2): the next stage's first
+    // substep sets rho_pp, rtheta_pp, rw_p, wwAvg (and ruAvg) before any task reads them; stage 0's vert_imp
+    // leaves b_tri / c_tri to stage 1's.  Their dead diagnostics (ntu 1 and 3): stage_diagnostics.  (ntu = 2:
+    // every diagnostic stored, 3: every acoustic state stored -- the A/Bs of these parts)
+    f.early_state_dead = c->ntu == 1 || c->ntu == 2;
+    f.early_diag_dead = c->ntu == 1 || c->ntu == 3;
+    // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
+    // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
+    f.solve0_dead = c->ntu && S.physics == 0 && !f.hf && f.rk_of[1] != 0;
+    // option ntu (reference semantics): the substep finish's rho_zz = rho_zz_old_split is the identity --
+    // this step's setup made rho_zz_old_split from rho_zz and nothing writes either in between -- not made
+    f.norz = f.early_state_dead && S.physics == 0 && S.LP == 64 && f.dynamics_split == 1;
+    // option stepkeep: the step whose launches the kept generation may thin out -- the headline's order
+    // (DESIGN.md §4k lists why each condition is there); anywhere else keep_gen stays 0
+    f.stepkeep = c->stepkeep && f.keep && c->ntu == 1 && c->defer4 && f.fcopy && c->accoef && !f.hf && !c->tmedge &&
+                 !c->etile && !c->transport && !c->forcing && f.rk_of[0] == 0 && f.rk_of[1] != 0 && f.rk_of[2] != 0;
+    // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
+    f.vik = c->vikeep && f.stepkeep;
+    // option a0keep: a full step leaves the next step's kdiff in X_kd0; a kept step takes it from there and runs
+    // neither stage 0's A nor the finish's edge part (stepkeep's step is the one whose stage 0 takes the
+    // form with setup's copies in A: fusecopy, ntu, defer4, horiz_mixing 0, undecomposed, no etile)
+    f.a0k = c->a0keep && f.stepkeep;
+    // option dynkeep: a kept step launches the guarded instances of stage 0's B, C and E and of stage 1's and 2's
+    // E, which decide on X_dkf; a full step clears the flag (in its setup task), a kept one sets it after stage
+    // 2's E (in that dyn_tend task): no timing key of its own.  (stepkeep = 2 skips those launches on the host)
+    f.dk = c->dynkeep && f.a0k && c->stepkeep == 1;
+    f.kept = gen >= 1;
+    // option stepkeep = 2, generation 2: everything stage 0's dyn_tend stores is in place from the
+    // generation-1 step (whose stage 0 read the diagnostics the step itself formed, as this one would)
+    // -- kdiff, tend_rho, dpdz, ru_save, u_2, the delsq fields, tend_u_euler, tend_w_euler, tend_theta_euler
+    // -- but w, which the acoustic launches and the later stages have rewritten since: restored below
+    // level L from that step's copy.  Stage 2 then forms tend_u, v and w alone: h_divergence (A) and the
+    // theta tendencies (B's flux, E) are final too, and tend_u_euler already holds its del4 part
+    f.keep2 = gen == 2 && c->stepkeep == 2;
+    return f;
+}
+
+// option smlkeep: X_smlS formed here when its inputs may have changed since the kernel last ran
+// (mpas_ctx::sml_valid): on the task stream ahead of the step and outside any capture, under the flux task's
+// timing key.  With dd0 the kernel reads nothing a step writes; without it X_Dd comes from rw alone (the setup
+// that follows stores rw_save = rw, and no task of the step writes rw), so ahead of the setup is the same computation
+void sml_ensure(mpas_ctx* c, const StepForm& f) {
+    if (!f.keep || c->sml_valid) return;
     run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(c->S, c->stream, c->dd0 ? 2 : 1); });
     c->sml_valid = true;
 }
 
-// the rk_step argument of stage s's dyn_tend (Q4: the reference driver passes the stage's time step)
-int srk3_rk_of(double dt, int schedule, int s) {
-    const double sub[3] = {dt / 3, dt / 2, dt / 2};
-    return schedule == 0 ? (int)sub[s] : s;
-}
-// option stepkeep: the step whose launches the kept generation may thin out -- the headline's order
-// (DESIGN.md §4k lists why each condition is there); anywhere else keep_gen stays 0
-bool stepkeep_active(const mpas_ctx* c, double dt, int schedule) {
-    return c->stepkeep && smlkeep_active(c) && c->ntu == 1 && c->defer4 && c->fusesetup && c->fusecopy && c->accoef &&
-           !hfuse_active(c) && !c->tmedge && !c->etile && !c->transport && !c->forcing &&
-           srk3_rk_of(dt, schedule, 0) == 0 && srk3_rk_of(dt, schedule, 1) != 0 && srk3_rk_of(dt, schedule, 2) != 0;
+DynTendArgs stage_args(const StepForm& f, int r) {
+    DynTendArgs a{};
+    a.rk_step = f.rk_of[r];
+    a.dt = f.dt;
+    a.horiz_mixing = 0, a.cam_coef = 0.0, a.mix_full = 0, a.rayleigh_damp_u = 0;  // constants.rg:57 "2d_smagorinsky"
+    a.exact_q = f.exact;
+    a.tme = f.tme;
+    a.hfuse = f.hf;
+    a.cp = (f.fcopy && r == 0) ? 1 : 0;
+    if (f.defer4) {
+        a.defer_out = (r < 2 && f.rk_of[r] == 0 && f.rk_of[r + 1] != 0) ? 1 : 0;
+        a.defer_in = (r > 0 && f.rk_of[r - 1] == 0 && f.rk_of[r] != 0) ? 1 : 0;
+        // (option ntu: the stages before the last read no tend_u_euler -- their edge kernels form no
+        // tend_u -- so the deferred del4 goes to the last stage's edge kernel, the first that reads it;
+        // its operands, delsq_divergence / delsq_vorticity / rho_edge, are unchanged until then)
+        if (f.ntu) a.defer_in = (r == 2 && f.d4_pending) ? 1 : 0;
+    }
+    // option ntu (reference semantics): a stage before the step's last leaves dead tendencies -- the last
+    // stage rewrites tend_u, tend_theta, tend_rtheta_adv and rthdynten, and no task in between reads them
+    // (set_smlstep reads u_tend, Q2; the acoustic step reads neither tend_u, Q18, nor tend_theta: theta_m
+    // is its tend_rt, Q8): that dyn_tend forms none of them (tend_u only where its D, reading it, does not run)
+    if (f.ntu && f.physics == 0 && r < 2) {
+        a.nth = 1;
+        a.ntu = 1;  // (launch_dyn_tend keeps it off where D runs in the call)
+    }
+    if (f.mru && f.number_sub_steps[r] > 0) a.rud = f.rk_sub_timestep[r];
+    if (f.msml) a.smlE = 1;
+    return a;
 }
 
-// gen: the kept generation the step runs at (option stepkeep; 0: every launch of the step)
-void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
-    // rk_timestep.rg:378-399
-    const int number_of_sub_steps = 2;
-    const int dynamics_split = 1;  // constants.rg:62
-    const double dt_dynamics = dt;
-    const double rk_sub_timestep[3] = {dt_dynamics / 3, dt_dynamics / number_of_sub_steps,
-                                       dt_dynamics / number_of_sub_steps};
-    int number_sub_steps[3];
-    number_sub_steps[0] = (number_of_sub_steps / 2 > 1) ? number_of_sub_steps / 2 : 1;
-    number_sub_steps[1] = number_sub_steps[0];
-    number_sub_steps[2] = number_of_sub_steps;
+struct StepRun {
+    FuseBuffers fb;
+    bool pending = false;     // a damping waits for the next acoustic launch (option fusedamp), with coef_prev
+    double coef_prev = 0.0;
+    int done_acoustic = 0;
+    double dts_vi = 0.0;      // the dts of the launch that formed the live vert_imp coefficient set (option accoef)
+    bool vi_done = false;     // stage 1's vert_imp ran beside stage 0's solve_diagnostics edges (option hfuse)
+    bool vc_done = false;     // the stage's solve_diagnostics vertex / cell kernel ran beside its last acoustic launch
+    bool a_done = false;      // the stage's dyn_tend A ran in the launch before it
+    bool vdyn_on = false;     // stage 2's dyn_tend stores v (decided there: S.eoe_same is k_prepare's, which the
+                              // step's first task may still have to run)
+    bool flux_done = false;   // (option smlsum: the step's flux sum, beside setup and A on small grids)
+    explicit StepRun(mpas_ctx* c) : fb(c) {}
+};
+
+// :400-424 -- the copy the transport starts from, the forcing, setup / moist / stage 0's vert_imp, the flux sum
+void step_begin(mpas_ctx* c, const StepForm& f, StepRun& r) {
     const DevState& S = c->S;
     hipStream_t st = c->stream;
-    // option trsave: the copy below folded into the transport's bounds kernel (its tables decided here:
-    // the tiled and LDS-edge forms need none of them built, su stored)
-    // (transport = 2: the separate copy -- its first stage reads scalars and scalars_old)
-    const bool trfold = c->transport == 1 && c->trsave && !c->halo && !c->trtile && !c->tredge && !S.trsu;
-    if (c->transport && !trfold) {
+    const double dts0 = f.rk_sub_timestep[0];
+    if (c->transport && !f.trfold) {
         // the time level the transport starts from (MPAS-A scalars(time level 1)); the
         // copy carries the ghosts of scalars, fresh or not, so scalars_old is as stale
         run_task(c, "scalars_save", [&] {
@@ -1043,343 +1195,236 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
             return e;
         });
     }
-    // option fusecopy: ru_save / u_2 by stage 0's dyn_tend edge kernel (reads u and ru there;
-    // no task between the setup and that kernel reads ru_save or u_2, in any physics mode)
-    const bool fcopy = c->fusesetup && c->fusecopy;
-    // option fusedamp (reference semantics): each damping but the step's last is applied by
-    // the next acoustic launch (k_acoustic MODE 2), the last from the div the acoustic step
-    // stored (launch_div_damping_div); the same bits as the separate task.  Decomposed (option
-    // fusedamp_halo): the div is exchanged where rtheta_pp was, the ring-1 edges stay fresh
-    const bool fuse = c->fusedamp && S.physics == 0 && (!c->halo || (c->fusedamp_halo && S.ring1 && S.nERing >= S.nEO));
-    FuseBuffers fb(c);
-    int n_acoustic = 0, done_acoustic = 0;
-    for (int r = 0; r < 3; r++) n_acoustic += number_sub_steps[r] + (S.physics ? 0 : 1);
-    bool pending = false;
-    double coef_prev = 0.0;
-    // option tmedge (reference semantics, undecomposed): dyn_tend's edge kernel stores
-    // theta_m(cell2) + theta_m(cell1) per edge, which the stage's acoustic substeps and the
-    // damping read instead of gathering theta_m at both cells (theta_m unchanged in between)
-    const int tme = (c->tmedge && S.physics == 0 && !c->halo) ? 1 : 0;
-    // option hfuse (reference semantics, undecomposed): neighbouring kernels that neither
-    // read what the other writes share a launch (k_solve.hip combined launches, dyn_tend's
-    // rk 0 D beside E); the same values
-    const int hf = hfuse_active(c) ? 1 : 0;
-    bool vi_done = false;  // stage 1's vert_imp ran beside stage 0's solve_diagnostics edges
-    // hfuse with fusedamp (and the default epw, no tmedge): a stage's last acoustic launch
-    // beside its solve_diagnostics vertex / cell kernel, and the stage's edge kernel beside
-    // the next stage's dyn_tend A (k_acoustic.hip / k_dyn.hip combined launches)
-    const bool hf2 = hf && fuse && !tme && S.epw == 2;
-    bool vc_done = false, a_done = false, vdyn_on = false;
-    // option smlsum (fast path, with fusesml): the slope-flux sum of set_smlstep formed once per
-    // step (X_smlS); each stage's fused set_smlstep then reads one column instead of u_tend at
-    // the cell's edges and zb_cell / zb3_cell (none of them written within the step)
-    const bool smls = fuse && c->fusesml && c->smlsum && !c->exact && S.physics == 0;
-    // option smlkeep (undecomposed): srk3_step formed the sum ahead of the step where its inputs may have
-    // changed since it last did (sml_ensure) -- no flux launch here, so none in a captured step
-    const bool keep = smls && smlkeep_active(c);
-    // option dd0 (reference semantics): every acoustic launch takes rw_save - rw as 0.0 (ddx 2); without it
-    // the launches of a step with smlsum read the difference from X_Dd (ddx 1), the others both columns
-    const int ddx = (c->dd0 && S.physics == 0) ? 2 : smls ? 1 : 0;
-    const int fluxf = ddx == 2 ? 2 : 1;  // (the flux body beside the setup: with X_Dd or without)
-    auto stage_args = [&](int r) {
-        DynTendArgs a{};
-        a.rk_step = schedule == 0 ? (int)rk_sub_timestep[r] : r;  // Q4
-        a.dt = dt;
-        a.horiz_mixing = 0;  // constants.rg:57 "2d_smagorinsky"
-        a.cam_coef = 0.0;
-        a.mix_full = 0;
-        a.rayleigh_damp_u = 0;
-        a.exact_q = c->exact;
-        a.tme = tme;
-        a.hfuse = hf;
-        a.cp = (fcopy && r == 0) ? 1 : 0;
-        // option defer4: an rk_step 0 stage followed by an rk_step > 0 one leaves its kernel D
-        // (tend_u_euler's del4 part; its tend_u is dead: the next stage rewrites it and no task
-        // in between reads it in the reference semantics) to the next stage's edge kernel
-        auto rk_of = [&](int s) { return schedule == 0 ? (int)rk_sub_timestep[s] : s; };
-        if (c->defer4 && S.physics == 0) {
-            a.defer_out = (r < 2 && rk_of(r) == 0 && rk_of(r + 1) != 0) ? 1 : 0;
-            a.defer_in = (r > 0 && rk_of(r - 1) == 0 && rk_of(r) != 0) ? 1 : 0;
-            // (option ntu: the stages before the last read no tend_u_euler -- their edge kernels form no
-            // tend_u -- so the deferred del4 goes to the last stage's edge kernel, the first that reads it;
-            // its operands, delsq_divergence / delsq_vorticity / rho_edge, are unchanged until then)
-            if (c->ntu) {
-                const bool pending = (rk_of(0) == 0 && rk_of(1) != 0) || (rk_of(1) == 0 && rk_of(2) != 0);
-                a.defer_in = (r == 2 && pending) ? 1 : 0;
-            }
-        }
-        // option ntu (reference semantics): a stage before the step's last leaves dead tendencies -- the last
-        // stage rewrites tend_u, tend_theta, tend_rtheta_adv and rthdynten, and no task in between reads them
-        // (set_smlstep reads u_tend, Q2; the acoustic step reads neither tend_u, Q18, nor tend_theta: theta_m
-        // is its tend_rt, Q8): that dyn_tend forms none of them (tend_u only where its D, reading it, does not run)
-        if (c->ntu && S.physics == 0 && r < 2) {
-            a.nth = 1;
-            a.ntu = 1;  // (launch_dyn_tend keeps it off where D runs in the call)
-        }
-        // option mru (the MPAS dynamics, fast path): the kernel that forms the stage's final tend_u also
-        // stores the first acoustic substep's ru_p = dts tend_u and ruAvg = ru_p (nothing in between reads
-        // or writes them; set_smlstep reads tend_u only)
-        if (c->mru && S.physics == 2 && !c->exact && number_sub_steps[r] > 0) a.rud = rk_sub_timestep[r];
-        // option msml (the MPAS dynamics): the stage's set_smlstep (:1503-1528) applied by E to the tend_w it
-        // forms -- set_smlstep follows dyn_tend directly and reads tend_u, which B / D have finished
-        if (c->msml && S.physics == 2) a.smlE = 1;
-        return a;
-    };
-    // option accoef (reference semantics, where nothing writes theta_m within the step): every acoustic
-    // launch forms cofwr / coftz / a_tri itself, with the dts of the setup or vert_imp launch that formed
-    // the live coefficient set (dts_vi, recorded at each of those launches -- not the acoustic launch's own)
-    // (not with option tmedge, off by default: its launches keep loading the stored set -- the exact first
-    // launch of that form would lose a wave of occupancy to the three expressions, profiles/r08)
-    const int aco = (c->accoef && S.physics == 0 && !tme) ? 1 : 0;
-    double dts_vi = 0.0;
-    // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
-    const bool vik = c->vikeep && stepkeep_active(c, dt, schedule);
-    // option a0keep: a full step leaves the next step's kdiff in X_kd0; a kept step takes it from there and runs
-    // neither stage 0's A nor the finish's edge part (stepkeep_active's step is the one whose stage 0 takes the
-    // form with setup's copies in A: fusecopy, ntu, defer4, horiz_mixing 0, undecomposed, no etile)
-    const bool a0k = c->a0keep && stepkeep_active(c, dt, schedule);
-    // option dynkeep: a kept step launches the guarded instances of stage 0's B, C and E and of stage 1's and 2's
-    // E, which decide on X_dkf; a full step clears the flag (in its setup task), a kept one sets it after stage
-    // 2's E (in that dyn_tend task): no timing key of its own.  (stepkeep = 2 skips those launches on the host)
-    const bool dk = c->dynkeep && a0k && c->stepkeep == 1;
-    bool flux_done = false;  // (option smlsum: the step's flux sum, beside setup and A on small grids)
-    // option ntu: stage 0's solve_diagnostics is dead where stage 1 runs at rk_step > 0 (a stage before the last
-    // reads nothing it writes; an rk_step 0 stage 1 would read divergence and vorticity)
-    const int rk1 = schedule == 0 ? (int)rk_sub_timestep[1] : 1;
-    const bool solve0_dead = c->ntu && S.physics == 0 && !hf && rk1 != 0;
-    // option ntu (reference semantics): the substep finish's rho_zz = rho_zz_old_split is the identity --
-    // this step's setup made rho_zz_old_split from rho_zz and nothing writes either in between -- not made
-    const bool norz = (c->ntu == 1 || c->ntu == 2) && S.physics == 0 && S.LP == 64 && dynamics_split == 1;
     // option forcing: the physics tendencies of the step, from the state the step starts from; every stage's
     // dyn_tend (the MPAS forms) reads them, no task of the step writes them
     if (c->forcing) run_task(c, "atm_held_suarez_forcing", [&] { return launch_held_suarez_forcing(S, st); });
-    if (c->fusesetup && S.physics == 0 && hf2) {  // + stage 0's dyn_tend A in the same launch
-        const bool fl = smls && !keep;
+    if (c->fusesetup && S.physics == 0 && f.hf2) {  // + stage 0's dyn_tend A in the same launch
+        const bool fl = f.smls && !f.keep;
         run_task(c, fl ? "hfuse[setup+dyn_A+sml_flux]" : "hfuse[setup+dyn_A]", [&] {
-            return launch_hf_setup_dyn_A(S, st, stage_args(0), rk_sub_timestep[0], fcopy ? 0 : 1, fl ? fluxf : 0);
+            return launch_hf_setup_dyn_A(S, st, stage_args(f, 0), dts0, f.fcopy ? 0 : 1, fl ? f.fluxf : 0);
         });
-        dts_vi = rk_sub_timestep[0];
-        a_done = true;
-        flux_done = fl;
+        r.a_done = true;
+        r.flux_done = fl;
     } else if (c->fusesetup) {  // :404-417 as one column-local launch (same values; MPAS forms under physics)
         // (option ntu: stage 0's vert_imp leaves b_tri / c_tri unstored -- no task reads them and stage 1's
         // vert_imp, which always runs, rewrites both; "-bc")
-        const bool nbc = c->ntu == 1 || c->ntu == 2;
-        run_task(c, fcopy ? (nbc ? "atm_rk_integration_setup[cells+moist+vert_imp-bc]" : "atm_rk_integration_setup[cells+moist+vert_imp]")
-                          : (nbc ? "atm_rk_integration_setup[+moist+vert_imp-bc]" : "atm_rk_integration_setup[+moist+vert_imp]"),
-                 [&] {
-                     if (dk && gen == 0) {  // (the columns of option dynkeep are stale from here on)
-                         const hipError_t e = launch_dk_flag(S, st, 0);
-                         if (e != hipSuccess) return e;
-                     }
-                     return launch_setup_moist_vert_imp(S, st, rk_sub_timestep[0], !fcopy, nbc ? 1 : 0, aco, gen >= 1 ? 1 : 0,
-                                                        vik ? 1 : 0, a0k && gen >= 1 ? 1 : 0);
-                 });
-        dts_vi = rk_sub_timestep[0];
+        const bool nbc = f.early_state_dead;
+        const char* key = f.fcopy ? "atm_rk_integration_setup[cells+moist+vert_imp]" : "atm_rk_integration_setup[+moist+vert_imp]";
+        run_task(c, tagged(key, nbc ? "-bc" : "").c_str(), [&] {
+            if (f.dk && f.gen == 0) {  // (the columns of option dynkeep are stale from here on)
+                const hipError_t e = launch_dk_flag(S, st, 0);
+                if (e != hipSuccess) return e;
+            }
+            return launch_setup_moist_vert_imp(S, st, dts0, !f.fcopy, nbc ? 1 : 0, f.aco, f.kept ? 1 : 0, f.vik ? 1 : 0,
+                                               f.a0k && f.kept ? 1 : 0);
+        });
     } else {
         run_task(c, "atm_rk_integration_setup", [&] { return launch_rk_integration_setup(S, st); });
         run_task(c, "atm_compute_moist_coefficients", [&] { return launch_moist_coefficients(S, st); });
-        run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, rk_sub_timestep[0]); });
-        dts_vi = rk_sub_timestep[0];
+        run_task(c, "atm_compute_vert_imp_coefs", [&] { return launch_vert_imp_coefs(S, st, dts0); });
     }
-    if (smls && !keep && !flux_done)
-        run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st, ddx == 2 ? 2 : 0); });
-    for (int rk_step = 0; rk_step < 3; rk_step++) {  // :426-477
-        if (rk_step == 1 && !vi_done) {
-            // (option vikeep, a kept step: a_tri, b_tri, c_tri and the four cof columns hold this call's values)
-            run_task(c, "atm_compute_vert_imp_coefs", [&] {
-                return vik && gen >= 1 ? launch_vert_imp_kept(S, st, rk_sub_timestep[rk_step])
-                                       : launch_vert_imp_coefs(S, st, rk_sub_timestep[rk_step]);
-            });
-            dts_vi = rk_sub_timestep[rk_step];
-        }
-        DynTendArgs a = stage_args(rk_step);
-        a.skipA = a_done ? 1 : 0;
-        // option vdyn (reference semantics): the last stage's v (:429-437) is reconstructed by its
-        // dyn_tend edge kernel from the edgesOnEdge u it gathers for q -- u is not written between
-        // that kernel and the stage's solve_diagnostics, which then skips v
-        if (rk_step == 2) vdyn_on = c->vdyn && S.physics == 0 && a.rk_step > 0 && S.eoe_same;
-        a.store_v = (rk_step == 2 && vdyn_on) ? 1 : 0;
-        a_done = false;
-        // option stepkeep = 2, generation 2: everything stage 0's dyn_tend stores is in place from the
-        // generation-1 step (whose stage 0 read the diagnostics the step itself formed, as this one would)
-        // -- kdiff, tend_rho, dpdz, ru_save, u_2, the delsq fields, tend_u_euler, tend_w_euler, tend_theta_euler
-        // -- but w, which the acoustic launches and the later stages have rewritten since: restored below
-        // level L from that step's copy.  Stage 2 then forms tend_u, v and w alone: h_divergence (A) and the
-        // theta tendencies (B's flux, E) are final too, and tend_u_euler already holds its del4 part
-        const bool keep2 = gen == 2 && c->stepkeep == 2;
-        if (keep2 && rk_step == 2) {
-            a.skipA = 1;
-            a.defer_in = 0;
-            a.nth = 1;
-        }
-        // option stepkeep, any kept step: stage 2's A (rk_step > 0: h_divergence alone, from ru and the mesh --
-        // no task of the step writes ru) stored the same bits in the full step; B reads them
-        if (gen >= 1 && rk_step == 2) a.skipA = 1;
-        // option a0keep, any kept step: stage 0's A stored the same bits in the step before -- tend_rho, dpdz,
-        // X_wc, ru_save, u_2 -- and the setup launch has put the step's kdiff in place; B as if A had run
-        if (a0k && gen >= 1 && rk_step == 0) a.keptA = 1;
-        // option dynkeep, any kept step: the guarded instances -- the first kept step after a full one runs them as
-        // the plain ones and fills X_tue0 / X_w0..2, the later ones copy those back (the same launches: one graph)
-        const bool dkept = dk && gen >= 1;
-        if (dkept) a.dynkeep = rk_step + 1;
-        // timing key: the variant's read / write set (bench.py parses the tags)
-        const std::string dname = std::string("atm_compute_dyn_tend_work[") + (a.rk_step == 0 ? "rk0" : "rk>0") +
-                                  (a.cp ? "+copy" : "") + (a.defer_out ? "+d4o" : "") + (a.ntu ? "+ntu" : "") + (a.defer_in ? "+d4i" : "") +
-                                  (a.store_v ? "+v" : "") + (a.rud != 0.0 ? "+ru" : "") + (a.smlE ? "+sml" : "") +
-                                  (a.skipA || a.keptA ? "-A" : "") + "]";
-        if (keep2 && rk_step == 0) {
-            run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
-        } else {
-            run_task(c, dname.c_str(), [&] {
-                const hipError_t e = launch_dyn_tend(S, st, a);
-                // (option dynkeep: the step's last guarded launch is behind -- the columns hold this step's values)
-                return (dkept && rk_step == 2 && e == hipSuccess) ? launch_dk_flag(S, st, 1) : e;
-            });
-            if (gen == 1 && c->stepkeep == 2 && rk_step == 0)  // (the copy a generation-2 step restores)
-                run_task(c, "stepkeep_save_w", [&] { return launch_cell_col_copy(S, st, F_w, X_w0); });
-        }
-        const bool ru_done = a.rud != 0.0;  // (option mru: the first substep's ru_p / ruAvg stored)
-        // option fusesml (with fusedamp): the stage's first acoustic launch runs it first
-        const bool sml = fuse && c->fusesml;
-        if (!sml && !a.smlE)  // (option msml: run by E)
-            run_task(c, "atm_set_smlstep_pert_variables_work", [&] { return launch_set_smlstep(S, st, c->exact); });
-        const int n_small = number_sub_steps[rk_step] + (S.physics ? 0 : 1);  // Q5 (the MPAS form: n)
-        for (int small_step = 0; small_step < n_small; small_step++) {
-            const double dts = rk_sub_timestep[rk_step];
-            if (fuse) {
-                const int mode = pending ? 2 : 1;
-                const int sm = (sml && small_step == 0) ? (smls ? 2 : 1) : 0;
-                // rtheta_pp_old is read by the separate damping only: the fused one reads the
-                // stored div, so the step's last substep alone leaves it (option fusedamp)
-                // option ntu (bit 1): a stage's last substep before the step's last stage leaves rho_pp,
-                // rtheta_pp, rw_p and wwAvg unstored -- the next stage's first substep sets them before
-                // any task reads them (:1615-1636), and the damping reads the stored div
-                const int nst = (c->ntu == 1 || c->ntu == 2) && rk_step < 2 && small_step == n_small - 1 ? 2 : 0;
-                const int wold = ((done_acoustic + 1 == n_acoustic) ? 1 : 0) | nst;
-                if (hf2 && rk_step < 2 && mode == 2 && small_step > 0 && small_step == n_small - 1) {
-                    run_task(c, nst ? "hfuse[acoustic-st+solve_vc]" : "hfuse[acoustic+solve_vc]", [&] {
-                        return launch_hf_acoustic_solve_vc(S, st, dts, small_step, c->exact, coef_prev, wold, ddx, aco,
-                                                           dts_vi);
-                    });
-                    vc_done = true;
-                } else {
-                    // ("-st": option ntu's launch that stores no acoustic state, bench.py's accounting)
-                    const std::string an = nst ? std::string(acoustic_name(small_step, pending, sm, !(wold & 1))).insert(
-                                                     std::strlen(acoustic_name(small_step, pending, sm, !(wold & 1))) - 1, "-st")
-                                               : std::string(acoustic_name(small_step, pending, sm, !(wold & 1)));
-                    run_task(c, an.c_str(), [&] {
-                        // option vikeep: stage 0's launches load cofwt / cofwz from the scratch pair -- a copy of
-                        // the state whose two field slots point there (the kernels are the same)
-                        DevState A = S;
-                        if (vik && rk_step == 0) A.f[F_cofwt] = S.f[X_cofwt0], A.f[F_cofwz] = S.f[X_cofwz0];
-                        return launch_acoustic(A, st, dts, small_step, c->exact, mode, coef_prev, tme, sm, wold, ddx, 0, 0,
-                                               aco, dts_vi);
-                    });
-                }
-                if (mode == 2) fb.swap_rup();
-                fb.swap_dv();  // this substep's div is read next from X_dvB
-                if (++done_acoustic == n_acoustic) {
-                    if (hf)  // beside the solve_diagnostics vertex / cell kernel that follows
-                        run_task(c, "hfuse[damp+solve_vc]", [&] { return launch_hf_damp_solve_vc(S, st, dts, tme); });
-                    else
-                        run_task(c, "atm_divergence_damping_3d", [&] { return launch_div_damping_div(S, st, dts, tme); });
-                    pending = false;
-                } else {
-                    pending = true;
-                    coef_prev = divdamp_coef(dts);
-                }
-                continue;
-            }
-            // option mdamp (the MPAS forms): the previous substep's damping in this substep's ru_p kernel, the
-            // stage's last one in the recover edge kernel -- each read-modify-write of ru_p goes
-            const bool md_fold = c->mdamp && S.physics;
-            const int mdp = (md_fold && small_step > 0) ? (small_step == 1 ? 2 : 1) : 0;
-            const double cprev = mdp ? divdamp_coef(dts) : 0.0;
-            // (option ntu: the last substep of a stage before the last leaves wwAvg unstored -- its recover
-            // does not read it (the averages are dead there) and the next stage's first substep sets it)
-            const bool nww = S.physics && (c->ntu == 1 || c->ntu == 2) && rk_step < 2 && small_step == n_small - 1;
-            const std::string an = std::string(mdp ? "atm_advance_acoustic_step_work[ss>0+damp]" : acoustic_name(small_step));
-            const std::string an1 = nww ? an.substr(0, an.size() - 1) + "-ww]" : an;
-            // ("-ru": option mru, this first substep's ru_p / ruAvg were stored by the stage's dyn_tend)
-            const std::string anw = (small_step == 0 && ru_done) ? an1.substr(0, an1.size() - 1) + "-ru]" : an1;
-            run_task(c, anw.c_str(), [&] {
-                return launch_acoustic(S, st, dts, small_step, c->exact, 0, cprev, tme, 0, nww ? 3 : 1, ddx, mdp,
-                                       (small_step == 0 && ru_done) ? 1 : 0, aco, dts_vi);
-            });
-            if (!md_fold)
-                run_task(c, "atm_divergence_damping_3d", [&] { return launch_div_damping(S, st, dts, small_step == 0); });
-        }
-        if (S.physics) {  // rk_timestep.rg:460, commented out in the reference (Q7)
-            // option ntu: a stage before the last leaves ruAvg / wwAvg dead -- the next stage's first
-            // acoustic substep sets both before any task reads them
-            const bool navg = (c->ntu == 1 || c->ntu == 2) && rk_step < 2;
-            // (option mdamp: the stage's last damping in the edge kernel; 2: that substep was the stage's first)
-            const int ns_r = number_sub_steps[rk_step];
-            const int dmp = (c->mdamp && ns_r > 0) ? (ns_r == 1 ? 2 : 1) : 0;
-            const std::string rn = std::string(navg ? (rk_step == 1 ? "atm_recover_large_step_variables_work[rk1-avg]"
-                                                                   : "atm_recover_large_step_variables_work[rk<2-avg]")
-                                                    : recover_name(rk_step));
-            const std::string rnd = dmp ? rn.substr(0, rn.size() - 1) + "+damp]" : rn;
-            run_task(c, rnd.c_str(), [&] {
-                return launch_recover_large_step(S, st, ns_r, rk_step, dt, navg ? 1 : 0, dmp, rk_sub_timestep[rk_step]);
-            });
-        }
-        if (gen >= 1) {
-            // option stepkeep: no solve_diagnostics launch -- its outputs are functions of u and h alone, which
-            // no task of the step writes: they hold what the last stage of the step before stored (stage 1's
-            // [live] outputs are bits of that full kernel's, option ntu's own identity; v as stage 2's B or
-            // that kernel stored it)
-        } else if (hf && fuse && rk_step == 2 && S.LP == 64 && !c->transport) {
-            // (the vertex / cell kernel ran beside the last damping) the edge kernel beside
-            // atm_rk_dynamics_substep_finish, which follows below
-            run_task(c, vdyn_on ? (norz ? "hfuse[solve_e-v+finish-rz]" : "hfuse[solve_e-v+finish]")
-                                : (norz ? "hfuse[solve_e+finish-rz]" : "hfuse[solve_e+finish]"),
-                     [&] { return launch_hf_solve_e_finish(S, st, vdyn_on ? 0 : 1, norz ? 1 : 0); });
-        } else if (hf && fuse && rk_step == 2) {
-            run_task(c, vdyn_on ? "atm_compute_solve_diagnostics[e-v]" : "atm_compute_solve_diagnostics[e]",
-                     [&] { return launch_solve_diagnostics(S, st, 0, 2, 2, vdyn_on ? 1 : 0); });
-        } else if (hf2 && vc_done && rk_step < 2) {
-            // (the vertex / cell kernel ran beside the last acoustic launch) the edge kernel
-            // beside the next stage's dyn_tend A, and after stage 0 beside stage 1's vert_imp
-            const DynTendArgs nx = stage_args(rk_step + 1);
-            run_task(c, rk_step == 0 ? "hfuse[solve_e+vert_imp+dyn_A]" : "hfuse[solve_e+dyn_A]", [&] {
-                return launch_hf_solve_e_dyn_A(S, st, nx, rk_step == 0 ? 1 : 0, rk_sub_timestep[1]);
-            });
-            if (rk_step == 0) vi_done = true;
-            if (rk_step == 0) dts_vi = rk_sub_timestep[1];
-            a_done = true;
-            vc_done = false;
-        } else if (rk_step == 0 && solve0_dead) {
-            // option ntu: stage 0's solve_diagnostics is dead -- stage 1's dyn_tend (a stage before the last:
-            // no A, no tend_u) reads none of its outputs, no other task reads them, and stage 1's and 2's
-            // solve_diagnostics rewrite every one (h_edge, ke_edge, pv_edge, divergence, ke, vorticity, pv_vertex)
-        } else if (hf && rk_step == 0) {  // the edge kernel beside stage 1's vert_imp
-            run_task(c, "atm_compute_solve_diagnostics[vc]", [&] { return launch_solve_diagnostics(S, st, 0, 0, 1); });
-            run_task(c, "hfuse[solve_e+vert_imp]",
-                     [&] { return launch_hf_solve_e_vert_imp(S, st, rk_sub_timestep[1]); });
-            vi_done = true;
-            dts_vi = rk_sub_timestep[1];
-        } else {
-            const int nv = (rk_step == 2 && vdyn_on) ? 1 : 0;
-            // option ntu: a call before the last stage's, the next stage at rk_step > 0, stores only what
-            // that stage reads -- ke and pv_edge (the MPAS forms: rho_edge too); its divergence, vorticity,
-            // h_edge and ke_edge have no reader before the last stage's solve_diagnostics rewrites them
-            // (dyn_tend reads divergence and vorticity at rk_step 0 only; nothing reads h_edge, ke_edge)
-            const int rk_next = rk_step == 2 ? 0 : schedule == 0 ? (int)rk_sub_timestep[rk_step + 1] : rk_step + 1;
-            // (ntu = 2: every diagnostic stored, 3: every acoustic state stored -- the A/Bs of these parts)
-            const bool live = (c->ntu == 1 || c->ntu == 3) && rk_step < 2 && rk_next != 0;
-            run_task(c, live ? "atm_compute_solve_diagnostics[live]"
-                             : nv ? "atm_compute_solve_diagnostics[-v]" : "atm_compute_solve_diagnostics",
-                     [&] { return launch_solve_diagnostics(S, st, 0, rk_step, live ? 7 : 3, nv); });
-        }
+    r.dts_vi = dts0;
+    if (f.smls && !f.keep && !r.flux_done)
+        run_task(c, "atm_set_smlstep_pert_variables_work[flux]", [&] { return launch_sml_flux(S, st, f.ddx == 2 ? 2 : 0); });
+}
+
+// stage 1's vert_imp, where no combined launch has run it
+void stage_vert_imp(mpas_ctx* c, const StepForm& f, StepRun& r, int s) {
+    if (s != 1 || r.vi_done) return;
+    // (option vikeep, a kept step: a_tri, b_tri, c_tri and the four cof columns hold this call's values)
+    run_task(c, "atm_compute_vert_imp_coefs", [&] {
+        return f.vik && f.kept ? launch_vert_imp_kept(c->S, c->stream, f.rk_sub_timestep[s])
+                               : launch_vert_imp_coefs(c->S, c->stream, f.rk_sub_timestep[s]);
+    });
+    r.dts_vi = f.rk_sub_timestep[s];
+}
+
+// :427-428 -- the stage's dyn_tend and, without fusesml / msml, its set_smlstep; returns the call's arguments
+DynTendArgs stage_dyn_tend(mpas_ctx* c, const StepForm& f, StepRun& r, int s) {
+    const DevState& S = c->S;
+    hipStream_t st = c->stream;
+    DynTendArgs a = stage_args(f, s);
+    a.skipA = r.a_done ? 1 : 0;
+    // option vdyn (reference semantics): the last stage's v (:429-437) is reconstructed by its
+    // dyn_tend edge kernel from the edgesOnEdge u it gathers for q -- u is not written between
+    // that kernel and the stage's solve_diagnostics, which then skips v
+    if (s == 2) r.vdyn_on = c->vdyn && S.physics == 0 && a.rk_step > 0 && S.eoe_same;
+    a.store_v = (s == 2 && r.vdyn_on) ? 1 : 0;
+    r.a_done = false;
+    if (f.keep2 && s == 2) {  // (StepForm::keep2: tend_u, v and w alone)
+        a.skipA = 1;
+        a.defer_in = 0;
+        a.nth = 1;
     }
+    // option stepkeep, any kept step: stage 2's A (rk_step > 0: h_divergence alone, from ru and the mesh --
+    // no task of the step writes ru) stored the same bits in the full step; B reads them
+    if (f.kept && s == 2) a.skipA = 1;
+    // option a0keep, any kept step: stage 0's A stored the same bits in the step before -- tend_rho, dpdz,
+    // X_wc, ru_save, u_2 -- and the setup launch has put the step's kdiff in place; B as if A had run
+    if (f.a0k && f.kept && s == 0) a.keptA = 1;
+    // option dynkeep, any kept step: the guarded instances -- the first kept step after a full one runs them as
+    // the plain ones and fills X_tue0 / X_w0..2, the later ones copy those back (the same launches: one graph)
+    const bool dkept = f.dk && f.kept;
+    if (dkept) a.dynkeep = s + 1;
+    if (f.keep2 && s == 0) {  // (w below level L from the generation-1 step's copy; nothing else to form)
+        run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
+    } else {
+        run_task(c, dyn_tend_key(a).c_str(), [&] {
+            const hipError_t e = launch_dyn_tend(S, st, a);
+            // (option dynkeep: the step's last guarded launch is behind -- the columns hold this step's values)
+            return (dkept && s == 2 && e == hipSuccess) ? launch_dk_flag(S, st, 1) : e;
+        });
+        if (f.gen == 1 && c->stepkeep == 2 && s == 0)  // (the copy a generation-2 step restores)
+            run_task(c, "stepkeep_save_w", [&] { return launch_cell_col_copy(S, st, F_w, X_w0); });
+    }
+    if (!f.sml && !a.smlE)  // (option fusesml: run by the stage's first acoustic launch; option msml: by E)
+        run_task(c, "atm_set_smlstep_pert_variables_work", [&] { return launch_set_smlstep(S, st, c->exact); });
+    return a;
+}
+
+// :440-452 with option fusedamp: substep ss of stage s, the damping before it inside the launch
+void stage_acoustic_fused(mpas_ctx* c, const StepForm& f, StepRun& r, int s, int ss) {
+    const DevState& S = c->S;
+    hipStream_t st = c->stream;
+    const double dts = f.rk_sub_timestep[s];
+    const bool last_of_stage = ss == f.n_small[s] - 1;
+    const int mode = r.pending ? 2 : 1;
+    const int sm = (f.sml && ss == 0) ? (f.smls ? 2 : 1) : 0;
+    // rtheta_pp_old is read by the separate damping only: the fused one reads the
+    // stored div, so the step's last substep alone leaves it (option fusedamp)
+    // option ntu (bit 1): a stage's last substep before the step's last stage leaves rho_pp,
+    // rtheta_pp, rw_p and wwAvg unstored -- the next stage's first substep sets them before
+    // any task reads them (:1615-1636), and the damping reads the stored div
+    const int nst = f.early_state_dead && s < 2 && last_of_stage ? 2 : 0;
+    const int wold = ((r.done_acoustic + 1 == f.n_acoustic) ? 1 : 0) | nst;
+    if (f.hf2 && s < 2 && mode == 2 && ss > 0 && last_of_stage) {
+        run_task(c, nst ? "hfuse[acoustic-st+solve_vc]" : "hfuse[acoustic+solve_vc]", [&] {
+            return launch_hf_acoustic_solve_vc(S, st, dts, ss, c->exact, r.coef_prev, wold, f.ddx, f.aco, r.dts_vi);
+        });
+        r.vc_done = true;
+    } else {
+        // ("-st": option ntu's launch that stores no acoustic state, bench.py's accounting)
+        run_task(c, tagged(acoustic_name(ss, r.pending, sm, !(wold & 1)), nst ? "-st" : "").c_str(), [&] {
+            // option vikeep: stage 0's launches load cofwt / cofwz from the scratch pair -- a copy of
+            // the state whose two field slots point there (the kernels are the same)
+            DevState A = S;
+            if (f.vik && s == 0) A.f[F_cofwt] = S.f[X_cofwt0], A.f[F_cofwz] = S.f[X_cofwz0];
+            return launch_acoustic(A, st, dts, ss, c->exact, mode, r.coef_prev, f.tme, sm, wold, f.ddx, 0, 0, f.aco,
+                                   r.dts_vi);
+        });
+    }
+    if (mode == 2) r.fb.swap_rup();
+    r.fb.swap_dv();  // this substep's div is read next from X_dvB
+    if (++r.done_acoustic == f.n_acoustic) {
+        if (f.hf)  // beside the solve_diagnostics vertex / cell kernel that follows
+            run_task(c, "hfuse[damp+solve_vc]", [&] { return launch_hf_damp_solve_vc(S, st, dts, f.tme); });
+        else
+            run_task(c, "atm_divergence_damping_3d", [&] { return launch_div_damping_div(S, st, dts, f.tme); });
+        r.pending = false;
+    } else {
+        r.pending = true;
+        r.coef_prev = divdamp_coef(dts);
+    }
+}
+
+// :440-452 without it: the substep, then its damping (option mdamp: folded into the launch that next reads ru_p)
+void stage_acoustic_split(mpas_ctx* c, const StepForm& f, StepRun& r, int s, int ss, bool ru_done) {
+    const DevState& S = c->S;
+    hipStream_t st = c->stream;
+    const double dts = f.rk_sub_timestep[s];
+    const int mdp = (f.md_fold && ss > 0) ? (ss == 1 ? 2 : 1) : 0;
+    const double cprev = mdp ? divdamp_coef(dts) : 0.0;
+    // (option ntu: the last substep of a stage before the last leaves wwAvg unstored -- its recover
+    // does not read it (the averages are dead there) and the next stage's first substep sets it)
+    const bool nww = S.physics && f.early_state_dead && s < 2 && ss == f.n_small[s] - 1;
+    // ("-ru": option mru, this first substep's ru_p / ruAvg were stored by the stage's dyn_tend)
+    const bool nru = ss == 0 && ru_done;
+    const std::string an = tagged(tagged(acoustic_name(ss, mdp != 0), nww ? "-ww" : ""), nru ? "-ru" : "");
+    run_task(c, an.c_str(), [&] {
+        return launch_acoustic(S, st, dts, ss, c->exact, 0, cprev, f.tme, 0, nww ? 3 : 1, f.ddx, mdp, nru ? 1 : 0, f.aco,
+                               r.dts_vi);
+    });
+    if (!f.md_fold)
+        run_task(c, "atm_divergence_damping_3d", [&] { return launch_div_damping(S, st, dts, ss == 0); });
+}
+
+// rk_timestep.rg:460, commented out in the reference (Q7): the MPAS forms only
+void stage_recover(mpas_ctx* c, const StepForm& f, int s) {
+    if (!c->S.physics) return;
+    // option ntu: a stage before the last leaves ruAvg / wwAvg dead -- the next stage's first
+    // acoustic substep sets both before any task reads them
+    const bool navg = f.early_state_dead && s < 2;
+    // (option mdamp: the stage's last damping in the edge kernel; 2: that substep was the stage's first)
+    const int ns_r = f.number_sub_steps[s];
+    const int dmp = (c->mdamp && ns_r > 0) ? (ns_r == 1 ? 2 : 1) : 0;
+    const std::string rn = navg ? (s == 1 ? "atm_recover_large_step_variables_work[rk1-avg]"
+                                          : "atm_recover_large_step_variables_work[rk<2-avg]")
+                                : recover_name(s);
+    run_task(c, tagged(rn, dmp ? "+damp" : "").c_str(), [&] {
+        return launch_recover_large_step(c->S, c->stream, ns_r, s, f.dt, navg ? 1 : 0, dmp, f.rk_sub_timestep[s]);
+    });
+}
+
+// :462-476 -- the stage's solve_diagnostics, in the form the launches around it leave to it
+void stage_diagnostics(mpas_ctx* c, const StepForm& f, StepRun& r, int s) {
+    const DevState& S = c->S;
+    hipStream_t st = c->stream;
+    if (f.kept) {
+        // option stepkeep: no solve_diagnostics launch -- its outputs are functions of u and h alone, which
+        // no task of the step writes: they hold what the last stage of the step before stored (stage 1's
+        // [live] outputs are bits of that full kernel's, option ntu's own identity; v as stage 2's B or
+        // that kernel stored it)
+    } else if (s == 2 && f.finish_fused) {
+        // (the vertex / cell kernel ran beside the last damping) the edge kernel beside
+        // atm_rk_dynamics_substep_finish, which step_end then does not launch
+        run_task(c, tagged(r.vdyn_on ? "hfuse[solve_e-v+finish]" : "hfuse[solve_e+finish]", f.norz ? "-rz" : "").c_str(),
+                 [&] { return launch_hf_solve_e_finish(S, st, r.vdyn_on ? 0 : 1, f.norz ? 1 : 0); });
+    } else if (f.hf && f.fuse && s == 2) {
+        run_task(c, r.vdyn_on ? "atm_compute_solve_diagnostics[e-v]" : "atm_compute_solve_diagnostics[e]",
+                 [&] { return launch_solve_diagnostics(S, st, 0, 2, 2, r.vdyn_on ? 1 : 0); });
+    } else if (f.hf2 && r.vc_done && s < 2) {
+        // (the vertex / cell kernel ran beside the last acoustic launch) the edge kernel
+        // beside the next stage's dyn_tend A, and after stage 0 beside stage 1's vert_imp
+        const DynTendArgs nx = stage_args(f, s + 1);
+        run_task(c, s == 0 ? "hfuse[solve_e+vert_imp+dyn_A]" : "hfuse[solve_e+dyn_A]", [&] {
+            return launch_hf_solve_e_dyn_A(S, st, nx, s == 0 ? 1 : 0, f.rk_sub_timestep[1]);
+        });
+        if (s == 0) r.vi_done = true, r.dts_vi = f.rk_sub_timestep[1];
+        r.a_done = true;
+        r.vc_done = false;
+    } else if (s == 0 && f.solve0_dead) {
+        // option ntu: stage 0's solve_diagnostics is dead -- stage 1's dyn_tend (a stage before the last:
+        // no A, no tend_u) reads none of its outputs, no other task reads them, and stage 1's and 2's
+        // solve_diagnostics rewrite every one (h_edge, ke_edge, pv_edge, divergence, ke, vorticity, pv_vertex)
+    } else if (f.hf && s == 0) {  // the edge kernel beside stage 1's vert_imp
+        run_task(c, "atm_compute_solve_diagnostics[vc]", [&] { return launch_solve_diagnostics(S, st, 0, 0, 1); });
+        run_task(c, "hfuse[solve_e+vert_imp]", [&] { return launch_hf_solve_e_vert_imp(S, st, f.rk_sub_timestep[1]); });
+        r.vi_done = true;
+        r.dts_vi = f.rk_sub_timestep[1];
+    } else {
+        const int nv = (s == 2 && r.vdyn_on) ? 1 : 0;
+        // option ntu: a call before the last stage's, the next stage at rk_step > 0, stores only what
+        // that stage reads -- ke and pv_edge (the MPAS forms: rho_edge too); its divergence, vorticity,
+        // h_edge and ke_edge have no reader before the last stage's solve_diagnostics rewrites them
+        // (dyn_tend reads divergence and vorticity at rk_step 0 only; nothing reads h_edge, ke_edge)
+        const bool live = f.early_diag_dead && s < 2 && f.rk_of[s + 1] != 0;
+        run_task(c, live ? "atm_compute_solve_diagnostics[live]"
+                         : nv ? "atm_compute_solve_diagnostics[-v]" : "atm_compute_solve_diagnostics",
+                 [&] { return launch_solve_diagnostics(S, st, 0, s, live ? 7 : 3, nv); });
+    }
+}
+
+// :478-492 -- a0keep's kdiff for the next step, the transport, the reconstruction, the substep finish
+void step_end(mpas_ctx* c, const StepForm& f, StepRun& r) {
+    const DevState& S = c->S;
+    hipStream_t st = c->stream;
+    const double dt = f.dt;
     // option a0keep, a full step that leaves generation 1: the kdiff stage 0's A of the next step would store --
     // from u and the v stage 2 has just left (its B, or solve_diagnostics) -- into X_kd0; the field keeps this
     // step's.  Kernel A itself, on a state whose kdiff slot points at the scratch column; its other stores write
     // the bytes they hold.  (Not a dyn_tend row: the step's three stay three)
-    if (a0k && gen == 0)
-        run_task(c, "a0keep_kdiff", [&] { return launch_dyn_A_kdiff(S, st, stage_args(0), X_kd0); });
+    if (f.a0k && f.gen == 0)
+        run_task(c, "a0keep_kdiff", [&] { return launch_dyn_A_kdiff(S, st, stage_args(f, 0), X_kd0); });
     if (c->transport == 2) {
         // MPAS's RK3 transport (dynamics and transport split): every stage from scalars_old with the
         // step's ruAvg / wwAvg / rho_zz_old_split, its high-order fluxes from the stage before
@@ -1390,19 +1435,35 @@ void srk3(mpas_ctx* c, double dt, int schedule, int gen = 0) {
             return launch_advance_scalars_mono_rk(S, st, dt);
         });
     } else if (c->transport)  // after the last stage's recover: ruAvg / wwAvg / rho_zz of the step
-        run_task(c, trfold ? "atm_advance_scalars_mono[save]" : "atm_advance_scalars_mono", [&] {
-            trt_ensure(c);  // (built before a capture by prepare_now)
-            return launch_advance_scalars_mono(S, st, dt, trfold ? 1 : 0);
+        run_task(c, f.trfold ? "atm_advance_scalars_mono[save]" : "atm_advance_scalars_mono", [&] {
+            trt_ensure(c);  // (built before a capture by prepare_mesh)
+            return launch_advance_scalars_mono(S, st, dt, f.trfold ? 1 : 0);
         });
     if (S.physics == 2)  // the MPAS dynamics: cell-centre winds for the next step's curvature
         run_task(c, "mpas_reconstruct_2d", [&] { return launch_reconstruct_2d(S, st, 1); });  // (:487, commented)
     // (option a0keep, a kept step: no physics 0 task writes ruAvg, so the edge part's ruAvg_split = ruAvg stored
     // the same bytes in the step before -- the cell part alone)
-    if (!(hf && fuse && S.LP == 64 && !c->transport))  // (else it ran beside solve_diagnostics' edges)
-        run_task(c, norz ? "atm_rk_dynamics_substep_finish[-rz]" : "atm_rk_dynamics_substep_finish",
-                 [&] { return launch_substep_finish(S, st, 1, dynamics_split, norz ? 1 : 0, a0k && gen >= 1 ? 1 : 0); });
-    fb.finish();
+    if (!f.finish_fused)  // (else it ran beside solve_diagnostics' edges)
+        run_task(c, f.norz ? "atm_rk_dynamics_substep_finish[-rz]" : "atm_rk_dynamics_substep_finish", [&] {
+            return launch_substep_finish(S, st, 1, f.dynamics_split, f.norz ? 1 : 0, f.a0k && f.kept ? 1 : 0);
+        });
+    r.fb.finish();
     // :492 summarize_timestep(cr, er, false, false, false) (constants.rg:67-69): prints only
+}
+
+void srk3(mpas_ctx* c, const StepForm& f) {
+    StepRun r(c);
+    step_begin(c, f, r);
+    for (int s = 0; s < 3; s++) {  // :426-477
+        stage_vert_imp(c, f, r, s);
+        const DynTendArgs a = stage_dyn_tend(c, f, r, s);
+        for (int ss = 0; ss < f.n_small[s]; ss++)
+            if (f.fuse) stage_acoustic_fused(c, f, r, s, ss);
+            else stage_acoustic_split(c, f, r, s, ss, a.rud != 0.0);
+        stage_recover(c, f, s);
+        stage_diagnostics(c, f, r, s);
+    }
+    step_end(c, f, r);
 }
 
 void graph_free(mpas_ctx::GraphEntry& g) {
@@ -1418,24 +1479,21 @@ void graph_drop(mpas_ctx* c) {
 }
 
 void prepare_now(mpas_ctx* c) {
-    if (c->dirty) {
-        hipcheck(launch_prepare(c->S, c->stream), "prepare");
-        c->self_ok = c->S.selfc;
-        c->S.selfc = c->self_ok && c->self_on;
-        c->dirty = false;
-    }
+    prepare_mesh(c);
     if (c->transport) trt_ensure(c);
     ett_ensure(c);
 }
 
-// one atm_srk3 step at kept generation gen: replayed from a captured HIP graph when possible
-void srk3_run(mpas_ctx* c, double dt, int schedule, int gen) {
+// one atm_srk3 step of form f: replayed from a captured HIP graph when possible
+void srk3_run(mpas_ctx* c, const StepForm& f) {
+    const double dt = f.dt;
+    const int schedule = f.schedule, gen = f.gen;
     Halo* h = c->halo.get();
     const bool halo_graph = h && !h->loop && (h->stub ? c->graph_halo != 0 : (h->rccl && c->graph_halo == 1)) &&
                             !c->graph_refused;
-    sml_ensure(c);
+    sml_ensure(c, f);
     if (!c->graph_on || c->timing || (h && !halo_graph)) {
-        srk3(c, dt, schedule, gen);
+        srk3(c, f);
         return;
     }
     prepare_now(c);  // (synchronous: never inside a capture)
@@ -1457,7 +1515,7 @@ void srk3_run(mpas_ctx* c, double dt, int schedule, int gen) {
         // a start state not seen before (e.g. the first step after an upload): one eager step
         if (c->seen_stale0.size() >= 16) c->seen_stale0.erase(c->seen_stale0.begin());
         c->seen_stale0.push_back(h->stale);
-        srk3(c, dt, schedule, gen);
+        srk3(c, f);
         return;
     }
     mpas_ctx::GraphEntry g;
@@ -1471,51 +1529,41 @@ void srk3_run(mpas_ctx* c, double dt, int schedule, int gen) {
         fl0 = h->fields_moved;
         h->capture_miss = false;
     }
+    // a decomposed step whose capture failed: nothing ran, so the halo bookkeeping goes back to the step's start
+    // and the step runs eagerly.  refused: the transport refused the capture (a communicator that cannot be
+    // captured) -- eager steps from now on (a real error repeats in the eager step)
+    auto eager_instead = [&](bool refused) {
+        h->stale = g.stale0;
+        h->exchanges = ex0;
+        h->fields_moved = fl0;
+        h->overlapped.clear();  // (the aborted step's overlap record and race flag too)
+        h->race.clear();
+        h->err.clear();
+        if (refused) (void)hipGetLastError(), c->graph_refused = true, c->graph_fallbacks++;
+        srk3(c, f);
+    };
     hipcheck(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
     try {
-        srk3(c, dt, schedule, gen);
+        srk3(c, f);
     } catch (...) {
         hipGraph_t gr = nullptr;
         (void)hipStreamEndCapture(c->stream, &gr);
         if (gr) (void)hipGraphDestroy(gr);
-        if (h) {  // nothing ran: the bookkeeping goes back to the step's start
-            h->stale = g.stale0;
-            h->exchanges = ex0;
-            h->fields_moved = fl0;
-            h->overlapped.clear();  // (the aborted step's overlap record and race flag too)
-            h->race.clear();
-            if (h->capture_miss) {  // a pack table not built yet (never built inside a capture)
-                h->capture_miss = false;
-                h->err.clear();
-                srk3(c, dt, schedule, gen);  // eagerly: builds it; the next step captures
-                return;
-            }
-            // the transport refused the capture (a communicator that cannot be captured):
-            // eager steps from now on, and the step again eagerly (a real error repeats there)
-            (void)hipGetLastError();
-            h->err.clear();
-            c->graph_refused = true;
-            c->graph_fallbacks++;
-            srk3(c, dt, schedule, gen);
-            return;
-        }
-        throw;
+        if (!h) throw;
+        // (capture_miss: a pack table not built yet, never built inside a capture -- the eager step builds it,
+        // the next step captures)
+        const bool miss = h->capture_miss;
+        h->capture_miss = false;
+        eager_instead(!miss);
+        return;
     }
     {
         const hipError_t ee = hipStreamEndCapture(c->stream, &g.graph);
         hipError_t ei = ee;
         if (ee == hipSuccess) ei = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-        if (h && (ee != hipSuccess || ei != hipSuccess)) {  // (as above: nothing ran)
+        if (h && (ee != hipSuccess || ei != hipSuccess)) {
             graph_free(g);
-            (void)hipGetLastError();
-            h->stale = g.stale0;
-            h->exchanges = ex0;
-            h->fields_moved = fl0;
-            h->overlapped.clear();
-            h->race.clear();
-            c->graph_refused = true;
-            c->graph_fallbacks++;
-            srk3(c, dt, schedule, gen);
+            eager_instead(true);
             return;
         }
         hipcheck(ee, "hipStreamEndCapture");
@@ -1539,21 +1587,204 @@ void srk3_run(mpas_ctx* c, double dt, int schedule, int gen) {
     c->graph_launches++;
 }
 
-
 // one atm_srk3 step, with option stepkeep's bookkeeping: the generation the step runs at, then the one it leaves
 void srk3_step(mpas_ctx* c, double dt, int schedule) {
-    const bool act = stepkeep_active(c, dt, schedule);
+    const bool act = step_form(c, dt, schedule, 0).stepkeep;
     if (!act || c->keep_dt != dt || c->keep_schedule != schedule) c->keep_gen = 0;
     // (the launches of generations 1 and 2 differ with stepkeep = 2 only: one captured graph for both otherwise)
     const int gen = (c->keep_gen == 2 && c->stepkeep != 2) ? 1 : c->keep_gen, next = c->keep_gen < 2 ? c->keep_gen + 1 : 2;
     c->keep_gen = 0;  // (a step that fails promises nothing)
-    srk3_run(c, dt, schedule, gen);
+    srk3_run(c, step_form(c, dt, schedule, gen));
     if (act) {
         c->keep_gen = next;
         c->keep_dt = dt;
         c->keep_schedule = schedule;
     }
 }
+
+// ---- options: one row per name; mpas_set_option and mpas_get_option walk the table ---------------------
+// How mpas_set_option treats a value (then the row's hook runs, then the value is stored):
+enum OptTreat {
+    O_BOOL,   // any value: stored as value ? 1 : 0
+    O_CLAMP,  // stored clamped to [lo, hi]
+    O_RANGE,  // refused with the row's text outside [lo, hi]
+    O_LIST,   // refused with the row's text unless one of the listed values
+    O_ANY,    // stored as given (xcd: speed only, and no caller passes what it has not measured)
+    O_QUERY,  // read-only: mpas_set_option does not know the name
+};
+using OptHook = void (*)(mpas_ctx*, int64_t&);  // preconditions (throws) and side effects of a set
+using OptGet = int64_t (*)(mpas_ctx*);
+struct OptRow {
+    const char* name;
+    OptTreat treat;
+    int mpas_ctx::*cm;  // where the value lives: a member of mpas_ctx ...
+    int DevState::*sm;  // ... or of DevState; neither: the hook stores it, and without get the name is set-only
+    int64_t lo, hi;     // (O_LIST: the listed values are list[0 .. lo))
+    const char* err;
+    OptHook hook;
+    OptGet get;  // the read-only queries, and values that live elsewhere
+    int64_t list[4];
+};
+OptRow opt(const char* name, int mpas_ctx::*m, OptTreat t, int64_t lo = 0, int64_t hi = 0, const char* err = nullptr,
+           OptHook hook = nullptr, OptGet get = nullptr) {
+    return {name, t, m, nullptr, lo, hi, err, hook, get, {}};
+}
+OptRow opt(const char* name, int DevState::*m, OptTreat t, int64_t lo = 0, int64_t hi = 0, const char* err = nullptr,
+           OptHook hook = nullptr, std::initializer_list<int64_t> list = {}) {
+    OptRow o{name, t, nullptr, m, lo, hi, err, hook, nullptr, {}};
+    std::copy(list.begin(), list.end(), o.list);
+    return o;
+}
+constexpr int mpas_ctx::*kNoMember = nullptr;
+OptRow query(const char* name, OptGet get) { return opt(name, kNoMember, O_QUERY, 0, 0, nullptr, nullptr, get); }
+
+void dirty_tiles(mpas_ctx* c, int64_t&) { c->trt_dirty = c->ett_dirty = true; }
+void dirty_ett(mpas_ctx* c, int64_t&) { c->ett_dirty = true; }
+const char* const kStubLatencyErr = "stub_latency_us: a stub-transport context and 0..100000 us";
+
+const OptRow kOptions[] = {
+    opt("exact", &mpas_ctx::exact, O_BOOL),
+    opt("graph", &mpas_ctx::graph_on, O_BOOL),
+    opt("fusedamp", &mpas_ctx::fusedamp, O_BOOL),
+    opt("fusesetup", &mpas_ctx::fusesetup, O_BOOL),
+    opt("fusecopy", &mpas_ctx::fusecopy, O_BOOL),
+    opt("defer4", &mpas_ctx::defer4, O_BOOL),
+    opt("ntu", &mpas_ctx::ntu, O_CLAMP, 0, 3),
+    opt("mdamp", &mpas_ctx::mdamp, O_BOOL),
+    opt("accoef", &mpas_ctx::accoef, O_RANGE, 0, 1, "accoef must be 0 or 1"),
+    opt("dd0", &mpas_ctx::dd0, O_RANGE, 0, 1, "dd0 must be 0 or 1"),
+    opt("smlkeep", &mpas_ctx::smlkeep, O_RANGE, 0, 1, "smlkeep must be 0 or 1"),
+    opt("stepkeep", &mpas_ctx::stepkeep, O_RANGE, 0, 2, "stepkeep must be 0, 1 or 2"),
+    opt("vikeep", &mpas_ctx::vikeep, O_RANGE, 0, 1, "vikeep must be 0 or 1"),
+    opt("a0keep", &mpas_ctx::a0keep, O_RANGE, 0, 1, "a0keep must be 0 or 1"),
+    opt("dynkeep", &mpas_ctx::dynkeep, O_RANGE, 0, 1, "dynkeep must be 0 or 1"),
+    opt("mru", &mpas_ctx::mru, O_BOOL),
+    opt("msml", &mpas_ctx::msml, O_BOOL),
+    opt("vdyn", &mpas_ctx::vdyn, O_BOOL),
+    opt("tmedge", &mpas_ctx::tmedge, O_BOOL),
+    opt("fusesml", &mpas_ctx::fusesml, O_BOOL),
+    opt("smlsum", &mpas_ctx::smlsum, O_BOOL),
+    opt("fusedamp_halo", &mpas_ctx::fusedamp_halo, O_BOOL),
+    opt("hfuse", &mpas_ctx::hfuse, O_CLAMP, 0, 2),
+    // (every value but 1 and 2 is 0: below by the clamp, above by the hook)
+    opt("graph_halo", &mpas_ctx::graph_halo, O_CLAMP, 0, 3, nullptr,
+        [](mpas_ctx* c, int64_t& v) {
+            if (v == 3) v = 0;
+            c->graph_refused = false;
+        }),
+    opt("stub_refuse_capture", kNoMember, O_BOOL, 0, 0, nullptr,
+               [](mpas_ctx* c, int64_t& v) {
+                   if (!c->halo || !c->halo->stub) throw Fail{MPAS_EINVAL, "stub_refuse_capture: a stub-transport context"};
+                   c->halo->stub_refuse_capture = (int)v;
+               }),
+    opt("stub_latency_us", kNoMember, O_RANGE, 0, 100000, kStubLatencyErr,
+               [](mpas_ctx* c, int64_t& v) {
+                   if (!c->halo || !c->halo->stub) throw Fail{MPAS_EINVAL, kStubLatencyErr};
+                   c->halo->stub_latency_us = (int)v;
+               },
+               [](mpas_ctx* c) -> int64_t { return c->halo ? c->halo->stub_latency_us : 0; }),
+    opt("xcd", &DevState::xcd, O_ANY),
+    opt("keep_check", &mpas_ctx::keep_check, O_BOOL),
+    opt("epw", &DevState::epw, O_LIST, 3, 0, "epw must be 1, 2 or 4", nullptr, {1, 2, 4}),
+    opt("vcmix", &DevState::vcmix, O_BOOL),
+    opt("physics", &DevState::physics, O_RANGE, 0, 2, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (!v) c->transport = 0;
+            if (v != 2) c->forcing = 0;
+            c->ett_dirty = true;
+        }),
+    opt("trorder_e", &DevState::troe, O_RANGE, 0, 1 << 20, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"),
+    opt("cve", &DevState::cve, O_LIST, 4, 0, "cve must be 0, 1, 4 or 8", nullptr, {0, 1, 4, 8}),
+    opt("bsplit", &DevState::bsplit, O_RANGE, 0, 2, "bsplit must be 0, 1 or 2"),
+    opt("trepw", &DevState::trepw, O_RANGE, 1, 2, "trepw must be 1 or 2"),
+    opt("trsu", &DevState::trsu, O_BOOL),
+    opt("trorder", &DevState::tro, O_RANGE, 0, 1 << 20, "trorder must be 0, 1 or a run length >= 2"),
+    opt("ring1", &DevState::ring1, O_BOOL),
+    opt("trtile", &mpas_ctx::trtile, O_BOOL, 0, 0, nullptr, dirty_tiles),
+    opt("trsave", &mpas_ctx::trsave, O_BOOL),
+    opt("tredge", &mpas_ctx::tredge, O_BOOL, 0, 0, nullptr, dirty_tiles),
+    opt("trtile_ghosts", &mpas_ctx::trt_ghosts, O_BOOL, 0, 0, nullptr, dirty_tiles),
+    opt("trtcells", &mpas_ctx::trt_cells, O_RANGE, 1, 256, "trtcells must be 1..256", dirty_tiles),
+    opt("trtclo", &mpas_ctx::trt_clo, O_RANGE, 1 + NF * (2 + AF), 120, "trtclo must be 67..120 (LDS columns)", dirty_tiles),
+    opt("etile", &mpas_ctx::etile, O_BOOL, 0, 0, nullptr, dirty_ett),
+    opt("etmode", &DevState::etm, O_RANGE, 0, 2, "etmode must be 0, 1 or 2"),
+    opt("etthreads", &DevState::etnt, O_LIST, 2, 0, "etthreads must be 256 or 512", nullptr, {256, 512}),
+    opt("etcells", &mpas_ctx::ett_cells, O_RANGE, 1, 40, "etcells must be 1..40 (a tile's edges index in one byte)", dirty_ett),
+    opt("etclo", &mpas_ctx::ett_clo, O_RANGE, 20, 160, "etclo must be 20..160 (LDS columns)", dirty_ett),
+    opt("transport", &mpas_ctx::transport, O_RANGE, 0, 2, "transport must be 0, 1 (one monotonic update) or 2 (RK3)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (v && !c->S.physics)
+                throw Fail{MPAS_EINVAL, "transport needs physics = 1 (it reads the recovered ruAvg, wwAvg, rho_zz)"};
+        }),
+    opt("forcing", &mpas_ctx::forcing, O_RANGE, 0, 1, "forcing must be 0 or 1 (Held-Suarez)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (v && c->S.physics != 2)
+                throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
+        }),
+    opt("overlap", &mpas_ctx::overlap, O_BOOL, 0, 0, nullptr,
+        [](mpas_ctx* c, int64_t& v) {
+            if (c->halo) c->halo->overlap = (int)v;
+        }),
+    opt("self", &mpas_ctx::self_on, O_BOOL, 0, 0, nullptr, [](mpas_ctx* c, int64_t& v) { c->S.selfc = c->self_ok && v; }),
+    opt("bounds_probe", kNoMember, O_ANY, 0, 0, nullptr,  // bounds-checked build only
+               [](mpas_ctx* c, int64_t& v) {
+#if MPAS_BOUNDS
+                   hipcheck(hipSetDevice(c->device), "hipSetDevice");
+                   hipcheck(launch_bounds_probe(c->S, c->stream, (int)v), "bounds_probe");
+#else
+                   throw Fail{MPAS_ENOTSUP, "bounds_probe needs the bounds-checked build (libmpasdyn_bounds.so)"};
+#endif
+               }),
+    // the read-only queries
+    query("tredge_active", [](mpas_ctx* c) -> int64_t { return trt_ensure(c), c->S.tre != nullptr; }),  // edge groups built for this mesh
+    query("tredge_irregular", [](mpas_ctx* c) -> int64_t { return trt_ensure(c), c->tre.nirr; }),
+    query("trtile_active", [](mpas_ctx* c) -> int64_t { return trt_ensure(c), c->S.trt ? 1 : 0; }),  // tiles built for this mesh
+    query("trtile_count", [](mpas_ctx* c) -> int64_t { return trt_ensure(c), c->trt.ntiles; }),
+    query("etile_active", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->S.ett ? 1 : 0; }),  // dyn_tend tiles built for this mesh
+    query("etile_count", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.ntiles; }),
+    query("etile_columns", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.nclo; }),  // closure columns staged per launch
+    query("etile_maxclo", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.maxclo; }),
+    query("stepkeep_gen", [](mpas_ctx* c) -> int64_t { return c->keep_gen; }),
+    query("dynkeep_fresh", [](mpas_ctx* c) -> int64_t {  // the device flag X_dkf
+        int fresh = 0;
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        hipcheck(hipMemcpyAsync(&fresh, c->S.f[X_dkf], sizeof(fresh), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        return fresh;
+    }),
+    query("eoe_same", [](mpas_ctx* c) -> int64_t { return prepare_now(c), c->S.eoe_same; }),
+    // (the switches of the step's form that do not depend on dt, schedule or generation)
+    query("hfuse_active", [](mpas_ctx* c) -> int64_t { return step_form(c, 0.0, 1, 0).hf; }),
+    query("fusedamp_active", [](mpas_ctx* c) -> int64_t { return step_form(c, 0.0, 1, 0).fuse; }),
+    query("graph_fallbacks", [](mpas_ctx* c) -> int64_t { return c->graph_fallbacks; }),
+    query("graph_refused", [](mpas_ctx* c) -> int64_t { return c->graph_refused ? 1 : 0; }),
+    query("graph_captures", [](mpas_ctx* c) -> int64_t { return c->graph_captures; }),
+    query("graph_launches", [](mpas_ctx* c) -> int64_t { return c->graph_launches; }),
+    query("halo_state", [](mpas_ctx* c) -> int64_t {  // hash of the halo bookkeeping (debug)
+        uint64_t hsh = 1469598103934665603ull;
+        if (c->halo)
+            for (uint8_t v : c->halo->stale) hsh = (hsh ^ v) * 1099511628211ull;
+        return (int64_t)(hsh >> 1);
+    }),
+    query("orphan_edges", [](mpas_ctx* c) -> int64_t { return prepare_now(c), c->S.n_orph; }),  // edges no cell lists (k_prepare)
+    query("bounds", [](mpas_ctx*) -> int64_t { return MPAS_BOUNDS; }),  // the bounds-checked build
+#if MPAS_BOUNDS
+    query("bounds_units", [](mpas_ctx*) -> int64_t {  // kernel units checking / registered
+        return ((int64_t)bounds_units() << 32) | (int64_t)bounds_tus().size();
+    }),
+#endif
+    query("selfc", [](mpas_ctx* c) -> int64_t {  // decided now (needs the mesh uploaded)
+        if (c->dirty) hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        return prepare_mesh(c), c->S.selfc;
+    }),
+};
+const OptRow* find_option(const char* name) {
+    if (name)
+        for (const OptRow& o : kOptions)
+            if (std::strcmp(o.name, name) == 0) return &o;
+    return nullptr;
+}
+Fail unknown_option(const char* name) { return Fail{MPAS_EINVAL, std::string("unknown option ") + (name ? name : "(null)")}; }
 
 }  // namespace
 
@@ -1688,280 +1919,31 @@ int mpas_get_stream(mpas_ctx* c, void** stream) {
 int mpas_set_option(mpas_ctx* c, const char* name, int64_t value) {
     return guarded(c, [&] {
         graph_drop(c);  // every option is baked into a captured step
-        if (name && std::strcmp(name, "exact") == 0) c->exact = value ? 1 : 0;
-        else if (name && std::strcmp(name, "graph") == 0) c->graph_on = value ? 1 : 0;
-        else if (name && std::strcmp(name, "fusedamp") == 0) c->fusedamp = value ? 1 : 0;
-        else if (name && std::strcmp(name, "fusesetup") == 0) c->fusesetup = value ? 1 : 0;
-        else if (name && std::strcmp(name, "fusecopy") == 0) c->fusecopy = value ? 1 : 0;
-        else if (name && std::strcmp(name, "defer4") == 0) c->defer4 = value ? 1 : 0;
-        else if (name && std::strcmp(name, "ntu") == 0) c->ntu = value < 0 ? 0 : value > 3 ? 3 : value;
-        else if (name && std::strcmp(name, "mdamp") == 0) c->mdamp = value ? 1 : 0;
-        else if (name && std::strcmp(name, "accoef") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "accoef must be 0 or 1"};
-            c->accoef = (int)value;
+        const OptRow* o = find_option(name);
+        if (!o || o->treat == O_QUERY) throw unknown_option(name);
+        int64_t v = value;
+        const bool listed = o->treat == O_LIST && std::find(o->list, o->list + o->lo, v) != o->list + o->lo;
+        switch (o->treat) {
+            case O_BOOL: v = v ? 1 : 0; break;
+            case O_CLAMP: v = v < o->lo ? o->lo : v > o->hi ? o->hi : v; break;
+            case O_RANGE: if (v < o->lo || v > o->hi) throw Fail{MPAS_EINVAL, o->err}; break;
+            case O_LIST: if (!listed) throw Fail{MPAS_EINVAL, o->err}; break;
+            default: break;
         }
-        else if (name && std::strcmp(name, "dd0") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "dd0 must be 0 or 1"};
-            c->dd0 = (int)value;
-        } else if (name && std::strcmp(name, "smlkeep") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "smlkeep must be 0 or 1"};
-            c->smlkeep = (int)value;
-        } else if (name && std::strcmp(name, "stepkeep") == 0) {
-            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "stepkeep must be 0, 1 or 2"};
-            c->stepkeep = (int)value;
-        } else if (name && std::strcmp(name, "vikeep") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "vikeep must be 0 or 1"};
-            c->vikeep = (int)value;
-        } else if (name && std::strcmp(name, "a0keep") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "a0keep must be 0 or 1"};
-            c->a0keep = (int)value;
-        } else if (name && std::strcmp(name, "dynkeep") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "dynkeep must be 0 or 1"};
-            c->dynkeep = (int)value;
-        }
-        else if (name && std::strcmp(name, "mru") == 0) c->mru = value ? 1 : 0;
-        else if (name && std::strcmp(name, "msml") == 0) c->msml = value ? 1 : 0;
-        else if (name && std::strcmp(name, "vdyn") == 0) c->vdyn = value ? 1 : 0;
-        else if (name && std::strcmp(name, "tmedge") == 0) c->tmedge = value ? 1 : 0;
-        else if (name && std::strcmp(name, "fusesml") == 0) c->fusesml = value ? 1 : 0;
-        else if (name && std::strcmp(name, "smlsum") == 0) c->smlsum = value ? 1 : 0;
-        else if (name && std::strcmp(name, "fusedamp_halo") == 0) c->fusedamp_halo = value ? 1 : 0;
-        else if (name && std::strcmp(name, "hfuse") == 0) c->hfuse = value < 0 ? 0 : value > 2 ? 2 : value;
-        else if (name && std::strcmp(name, "graph_halo") == 0) {
-            c->graph_halo = (value == 1 || value == 2) ? value : 0;
-            c->graph_refused = false;
-        } else if (name && std::strcmp(name, "stub_refuse_capture") == 0) {
-            if (!c->halo || !c->halo->stub) throw Fail{MPAS_EINVAL, "stub_refuse_capture: a stub-transport context"};
-            c->halo->stub_refuse_capture = value ? 1 : 0;
-        }
-        else if (name && std::strcmp(name, "stub_latency_us") == 0) {
-            if (!c->halo || !c->halo->stub || value < 0 || value > 100000)
-                throw Fail{MPAS_EINVAL, "stub_latency_us: a stub-transport context and 0..100000 us"};
-            c->halo->stub_latency_us = (int)value;
-        }
-        else if (name && std::strcmp(name, "xcd") == 0) c->S.xcd = (int)value;
-        else if (name && std::strcmp(name, "keep_check") == 0) c->keep_check = value ? 1 : 0;
-        else if (name && std::strcmp(name, "epw") == 0) {
-            if (value != 1 && value != 2 && value != 4) throw Fail{MPAS_EINVAL, "epw must be 1, 2 or 4"};
-            c->S.epw = (int)value;
-        } else if (name && std::strcmp(name, "vcmix") == 0) {
-            c->S.vcmix = value ? 1 : 0;
-        } else if (name && std::strcmp(name, "physics") == 0) {
-            if (value < 0 || value > 2)
-                throw Fail{MPAS_EINVAL, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)"};
-            c->S.physics = (int)value;
-            if (!value) c->transport = 0;
-            if (value != 2) c->forcing = 0;
-            c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "trorder_e") == 0) {
-            if (value < 0 || value > (1 << 20)) throw Fail{MPAS_EINVAL, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"};
-            c->S.troe = (int)value;
-        } else if (name && std::strcmp(name, "cve") == 0) {
-            if (value != 0 && value != 1 && value != 4 && value != 8) throw Fail{MPAS_EINVAL, "cve must be 0, 1, 4 or 8"};
-            c->S.cve = (int)value;
-        } else if (name && std::strcmp(name, "bsplit") == 0) {
-            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "bsplit must be 0, 1 or 2"};
-            c->S.bsplit = (int)value;
-        } else if (name && std::strcmp(name, "trepw") == 0) {
-            if (value != 1 && value != 2) throw Fail{MPAS_EINVAL, "trepw must be 1 or 2"};
-            c->S.trepw = (int)value;
-        } else if (name && std::strcmp(name, "trsu") == 0) {
-            c->S.trsu = value ? 1 : 0;
-        } else if (name && std::strcmp(name, "trorder") == 0) {
-            if (value < 0 || value > (1 << 20)) throw Fail{MPAS_EINVAL, "trorder must be 0, 1 or a run length >= 2"};
-            c->S.tro = (int)value;
-        } else if (name && std::strcmp(name, "ring1") == 0) {
-            c->S.ring1 = value ? 1 : 0;
-        } else if (name && std::strcmp(name, "trtile") == 0) {
-            c->trtile = value ? 1 : 0;
-            c->trt_dirty = c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "trsave") == 0) {
-            c->trsave = value ? 1 : 0;
-        } else if (name && std::strcmp(name, "tredge") == 0) {
-            c->tredge = value ? 1 : 0;
-            c->trt_dirty = c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "trtile_ghosts") == 0) {
-            c->trt_ghosts = value ? 1 : 0;
-            c->trt_dirty = c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "trtcells") == 0) {
-            if (value < 1 || value > 256) throw Fail{MPAS_EINVAL, "trtcells must be 1..256"};
-            c->trt_cells = (int)value;
-            c->trt_dirty = c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "trtclo") == 0) {
-            if (value < 1 + NF * (2 + AF) || value > 120) throw Fail{MPAS_EINVAL, "trtclo must be 67..120 (LDS columns)"};
-            c->trt_clo = (int)value;
-            c->trt_dirty = c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "etile") == 0) {
-            c->etile = value ? 1 : 0;
-            c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "etmode") == 0) {
-            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "etmode must be 0, 1 or 2"};
-            c->S.etm = (int)value;
-        } else if (name && std::strcmp(name, "etthreads") == 0) {
-            if (value != 256 && value != 512) throw Fail{MPAS_EINVAL, "etthreads must be 256 or 512"};
-            c->S.etnt = (int)value;
-        } else if (name && std::strcmp(name, "etcells") == 0) {
-            if (value < 1 || value > 40) throw Fail{MPAS_EINVAL, "etcells must be 1..40 (a tile's edges index in one byte)"};
-            c->ett_cells = (int)value;
-            c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "etclo") == 0) {
-            if (value < 20 || value > 160) throw Fail{MPAS_EINVAL, "etclo must be 20..160 (LDS columns)"};
-            c->ett_clo = (int)value;
-            c->ett_dirty = true;
-        } else if (name && std::strcmp(name, "transport") == 0) {
-            if (value < 0 || value > 2) throw Fail{MPAS_EINVAL, "transport must be 0, 1 (one monotonic update) or 2 (RK3)"};
-            if (value && !c->S.physics) throw Fail{MPAS_EINVAL, "transport needs physics = 1 (it reads the recovered ruAvg, wwAvg, rho_zz)"};
-            c->transport = (int)value;
-        } else if (name && std::strcmp(name, "forcing") == 0) {
-            if (value != 0 && value != 1) throw Fail{MPAS_EINVAL, "forcing must be 0 or 1 (Held-Suarez)"};
-            if (value && c->S.physics != 2)
-                throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
-            c->forcing = (int)value;
-        } else if (name && std::strcmp(name, "overlap") == 0) {
-            c->overlap = value ? 1 : 0;
-            if (c->halo) c->halo->overlap = c->overlap;
-        } else if (name && std::strcmp(name, "self") == 0) {
-            c->self_on = value ? 1 : 0;
-            c->S.selfc = c->self_ok && c->self_on;
-        } else if (name && std::strcmp(name, "bounds_probe") == 0) {  // bounds-checked build only
-#if MPAS_BOUNDS
-            hipcheck(hipSetDevice(c->device), "hipSetDevice");
-            hipcheck(launch_bounds_probe(c->S, c->stream, (int)value), "bounds_probe");
-#else
-            throw Fail{MPAS_ENOTSUP, "bounds_probe needs the bounds-checked build (libmpasdyn_bounds.so)"};
-#endif
-        } else throw Fail{MPAS_EINVAL, std::string("unknown option ") + (name ? name : "(null)")};
+        if (o->hook) o->hook(c, v);
+        if (o->cm) c->*(o->cm) = (int)v;
+        if (o->sm) c->S.*(o->sm) = (int)v;
     });
 }
 
 int mpas_get_option(mpas_ctx* c, const char* name, int64_t* value) {
     return guarded(c, [&] {
         if (!value) throw Fail{MPAS_EINVAL, "mpas_get_option: null value"};
-        if (name && std::strcmp(name, "exact") == 0) *value = c->exact;
-        else if (name && std::strcmp(name, "xcd") == 0) *value = c->S.xcd;
-        else if (name && std::strcmp(name, "keep_check") == 0) *value = c->keep_check;
-        else if (name && std::strcmp(name, "epw") == 0) *value = c->S.epw;
-        else if (name && std::strcmp(name, "vcmix") == 0) *value = c->S.vcmix;
-        else if (name && std::strcmp(name, "physics") == 0) *value = c->S.physics;
-        else if (name && std::strcmp(name, "transport") == 0) *value = c->transport;
-        else if (name && std::strcmp(name, "forcing") == 0) *value = c->forcing;
-        else if (name && std::strcmp(name, "trorder") == 0) *value = c->S.tro;
-        else if (name && std::strcmp(name, "trsu") == 0) *value = c->S.trsu;
-        else if (name && std::strcmp(name, "trepw") == 0) *value = c->S.trepw;
-        else if (name && std::strcmp(name, "cve") == 0) *value = c->S.cve;
-        else if (name && std::strcmp(name, "bsplit") == 0) *value = c->S.bsplit;
-        else if (name && std::strcmp(name, "trorder_e") == 0) *value = c->S.troe;
-        else if (name && std::strcmp(name, "trtile") == 0) *value = c->trtile;
-        else if (name && std::strcmp(name, "tredge") == 0) *value = c->tredge;
-        else if (name && std::strcmp(name, "trsave") == 0) *value = c->trsave;
-        else if (name && std::strcmp(name, "tredge_active") == 0) {  // edge groups built for this mesh
-            trt_ensure(c);
-            *value = c->S.tre != nullptr;
-        } else if (name && std::strcmp(name, "tredge_irregular") == 0) {
-            trt_ensure(c);
-            *value = c->tre.nirr;
-        }
-        else if (name && std::strcmp(name, "ring1") == 0) *value = c->S.ring1;
-        else if (name && std::strcmp(name, "trtcells") == 0) *value = c->trt_cells;
-        else if (name && std::strcmp(name, "trtile_ghosts") == 0) *value = c->trt_ghosts;
-        else if (name && std::strcmp(name, "trtclo") == 0) *value = c->trt_clo;
-        else if (name && std::strcmp(name, "trtile_active") == 0) {  // tiles built for this mesh
-            trt_ensure(c);
-            *value = c->S.trt ? 1 : 0;
-        } else if (name && std::strcmp(name, "trtile_count") == 0) {
-            trt_ensure(c);
-            *value = c->trt.ntiles;
-        }
-        else if (name && std::strcmp(name, "etile") == 0) *value = c->etile;
-        else if (name && std::strcmp(name, "etcells") == 0) *value = c->ett_cells;
-        else if (name && std::strcmp(name, "etmode") == 0) *value = c->S.etm;
-        else if (name && std::strcmp(name, "etthreads") == 0) *value = c->S.etnt;
-        else if (name && std::strcmp(name, "etclo") == 0) *value = c->ett_clo;
-        else if (name && std::strcmp(name, "etile_active") == 0) {  // dyn_tend tiles built for this mesh
-            ett_ensure(c);
-            *value = c->S.ett ? 1 : 0;
-        } else if (name && std::strcmp(name, "etile_count") == 0) {
-            ett_ensure(c);
-            *value = c->ett.ntiles;
-        } else if (name && std::strcmp(name, "etile_columns") == 0) {  // closure columns staged per launch
-            ett_ensure(c);
-            *value = c->ett.nclo;
-        } else if (name && std::strcmp(name, "etile_maxclo") == 0) {
-            ett_ensure(c);
-            *value = c->ett.maxclo;
-        }
-        else if (name && std::strcmp(name, "overlap") == 0) *value = c->overlap;
-        else if (name && std::strcmp(name, "fusedamp") == 0) *value = c->fusedamp;
-        else if (name && std::strcmp(name, "fusesetup") == 0) *value = c->fusesetup;
-        else if (name && std::strcmp(name, "fusecopy") == 0) *value = c->fusecopy;
-        else if (name && std::strcmp(name, "defer4") == 0) *value = c->defer4;
-        else if (name && std::strcmp(name, "ntu") == 0) *value = c->ntu;
-        else if (name && std::strcmp(name, "mdamp") == 0) *value = c->mdamp;
-        else if (name && std::strcmp(name, "accoef") == 0) *value = c->accoef;
-        else if (name && std::strcmp(name, "dd0") == 0) *value = c->dd0;
-        else if (name && std::strcmp(name, "smlkeep") == 0) *value = c->smlkeep;
-        else if (name && std::strcmp(name, "stepkeep") == 0) *value = c->stepkeep;
-        else if (name && std::strcmp(name, "vikeep") == 0) *value = c->vikeep;
-        else if (name && std::strcmp(name, "a0keep") == 0) *value = c->a0keep;
-        else if (name && std::strcmp(name, "stepkeep_gen") == 0) *value = c->keep_gen;  // (read-only)
-        else if (name && std::strcmp(name, "dynkeep") == 0) *value = c->dynkeep;
-        else if (name && std::strcmp(name, "dynkeep_fresh") == 0) {  // (read-only: the device flag X_dkf)
-            int fresh = 0;
-            hipcheck(hipSetDevice(c->device), "hipSetDevice");
-            hipcheck(hipMemcpyAsync(&fresh, c->S.f[X_dkf], sizeof(fresh), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-            hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-            *value = fresh;
-        }
-        else if (name && std::strcmp(name, "mru") == 0) *value = c->mru;
-        else if (name && std::strcmp(name, "msml") == 0) *value = c->msml;
-        else if (name && std::strcmp(name, "vdyn") == 0) *value = c->vdyn;
-        else if (name && std::strcmp(name, "eoe_same") == 0) {
-            prepare_now(c);
-            *value = c->S.eoe_same;
-        }
-        else if (name && std::strcmp(name, "tmedge") == 0) *value = c->tmedge;
-        else if (name && std::strcmp(name, "fusesml") == 0) *value = c->fusesml;
-        else if (name && std::strcmp(name, "smlsum") == 0) *value = c->smlsum;
-        else if (name && std::strcmp(name, "fusedamp_halo") == 0) *value = c->fusedamp_halo;
-        else if (name && std::strcmp(name, "hfuse") == 0) *value = c->hfuse;
-        else if (name && std::strcmp(name, "hfuse_active") == 0) *value = hfuse_active(c);
-        else if (name && std::strcmp(name, "graph_halo") == 0) *value = c->graph_halo;
-        else if (name && std::strcmp(name, "graph_fallbacks") == 0) *value = c->graph_fallbacks;
-        else if (name && std::strcmp(name, "graph_refused") == 0) *value = c->graph_refused ? 1 : 0;
-        else if (name && std::strcmp(name, "stub_latency_us") == 0) *value = c->halo ? c->halo->stub_latency_us : 0;
-        else if (name && std::strcmp(name, "halo_state") == 0) {  // hash of the halo bookkeeping (debug)
-            uint64_t hsh = 1469598103934665603ull;
-            if (c->halo)
-                for (uint8_t v : c->halo->stale) hsh = (hsh ^ v) * 1099511628211ull;
-            *value = (int64_t)(hsh >> 1);
-        }
-        else if (name && std::strcmp(name, "fusedamp_active") == 0)
-            *value = c->fusedamp && c->S.physics == 0 &&
-                     (!c->halo || (c->fusedamp_halo && c->S.ring1 && c->S.nERing >= c->S.nEO));
-        else if (name && std::strcmp(name, "orphan_edges") == 0) {  // edges no cell lists (k_prepare)
-            prepare_now(c);
-            *value = c->S.n_orph;
-        }
-        else if (name && std::strcmp(name, "self") == 0) *value = c->self_on;
-        else if (name && std::strcmp(name, "graph") == 0) *value = c->graph_on;
-        else if (name && std::strcmp(name, "graph_captures") == 0) *value = c->graph_captures;
-        else if (name && std::strcmp(name, "graph_launches") == 0) *value = c->graph_launches;
-        else if (name && std::strcmp(name, "bounds") == 0) *value = MPAS_BOUNDS;  // the bounds-checked build
-#if MPAS_BOUNDS
-        else if (name && std::strcmp(name, "bounds_units") == 0) {  // kernel units checking / registered
-            *value = ((int64_t)bounds_units() << 32) | (int64_t)bounds_tus().size();
-        }
-#endif
-        else if (name && std::strcmp(name, "selfc") == 0) {
-            if (c->dirty) {  // decide now (needs the mesh uploaded)
-                hipcheck(hipSetDevice(c->device), "hipSetDevice");
-                hipcheck(launch_prepare(c->S, c->stream), "prepare");
-                c->self_ok = c->S.selfc;
-                c->S.selfc = c->self_ok && c->self_on;
-                c->dirty = false;
-            }
-            *value = c->S.selfc;
-        } else throw Fail{MPAS_EINVAL, std::string("unknown option ") + (name ? name : "(null)")};
+        const OptRow* o = find_option(name);
+        if (o && o->get) *value = o->get(c);
+        else if (o && o->cm) *value = c->*(o->cm);
+        else if (o && o->sm) *value = c->S.*(o->sm);
+        else throw unknown_option(name);  // (the set-only names too)
     }, true);
 }
 
@@ -2341,7 +2323,7 @@ int mpas_atm_set_smlstep_pert_variables_work(mpas_ctx* c) {
     MPAS_TASK("atm_set_smlstep_pert_variables_work", launch_set_smlstep(c->S, c->stream, c->exact));
 }
 int mpas_atm_advance_acoustic_step_work(mpas_ctx* c, double dts, int small_step) {
-    MPAS_TASK(acoustic_name(small_step), launch_acoustic(c->S, c->stream, dts, small_step, c->exact));
+    MPAS_TASK(acoustic_name(small_step).c_str(), launch_acoustic(c->S, c->stream, dts, small_step, c->exact));
 }
 int mpas_atm_divergence_damping_3d(mpas_ctx* c, double dts) {
     MPAS_TASK("atm_divergence_damping_3d", launch_div_damping(c->S, c->stream, dts));
