@@ -370,6 +370,42 @@ int mpas_atm_advance_scalars_mono_rk(mpas_ctx* ctx, double dt);
  *       MPAS_EINVAL; default 0; reset to 0 when "physics" leaves 2) makes mpas_atm_srk3 run this
  *       task once per step, ahead of stage 0's setup: the tendencies are held over the three stages. */
 int mpas_atm_held_suarez_forcing(mpas_ctx* ctx);
+/* Time-mean statistics on sigma levels (k_stats.hip): what turns a forced run into a climate.  No reference
+ *       entry point.  One call of the task samples the state as found on every owned cell column and adds the
+ *       sample's first and second moments to per-cell fp64 accumulators ("physics" = 2, else MPAS_EINVAL; dry:
+ *       theta_m stands for theta).  Per owned cell c and level k < nVertLevels:
+ *         p(k) = pressure_base + pressure_p
+ *         ps   = mpas_atm_held_suarez_forcing's, term for term (atm_compute_output_diagnostics' surface pressure)
+ *         s(k) = p(k) / ps;   T(k) = theta_m(k) exner(k);   u(k) = uReconstructZonal, v(k) = uReconstructMeridional
+ *       and per configured target sigma_j (j < nsigma <= 64; lsig_j = log(sigma_j), glibc log on the host at
+ *       configure time):
+ *         kb  = the lowest k in 0..nVertLevels-2 with s(k) >= sigma_j > s(k+1), decided on s itself, never on its
+ *               logarithm (well defined for a column that is not monotone); none: the pair (c, j) takes no
+ *               sample in this call
+ *         a   = (lsig_j - log s(kb)) / (log s(kb+1) - log s(kb))
+ *         X_j = X(kb) + a (X(kb+1) - X(kb))            for X in u, v, T
+ *       The accumulators per (owned cell, j), each `acc += x` in call order: n (the sample count, as a double), u,
+ *       v, T, uu, vv, TT, uv, vT -- stat 0..8 of mpas_sigma_stats_read -- and per cell [sum ps, sum ps^2, calls]
+ *       (stat 9, three "levels").  They are not registry fields (mpas_field_count is unchanged); the task writes
+ *       no field.  No floating-point atomics and no reduction across cells: two runs give the same bits.
+ *       Statement order: tests/stats_ref.py (bit for bit but for log).  A decomposed context samples its owned
+ *       cells; no exchange is needed.
+ * mpas_sigma_stats_configure allocates and zeroes the accumulators for the nsigma targets sigma[0..nsigma)
+ *       (nsigma = 0 frees them and sets "stats_every" to 0); MPAS_EINVAL for nsigma outside 0..64, a sigma outside
+ *       (0, 1] or a list that does not decrease strictly.  mpas_sigma_stats_reset zeroes them.
+ * mpas_sigma_stats_read copies one accumulator of the owned cells to out (the call synchronises): element
+ *       (cell e, target j) at byte offset e*stride_cell + j*stride_level; stat 9: j = 0..2.
+ * Option "stats_every" = N >= 0 (default 0; N > 0 needs "physics" = 2 and configured targets, else MPAS_EINVAL; a
+ *       negative value: MPAS_EINVAL; reset to 0 when "physics" leaves 2) makes mpas_atm_srk3 run the task after
+ *       every N-th step since the option was set, behind the step's mpas_reconstruct_2d: launched on the stream
+ *       after the step (after the replay of a captured step -- the task is in no captured graph, so
+ *       "graph_captures" is what it is without the option), under its own timing key
+ *       "atm_sigma_stats_accumulate".  With 0 the step is launch for launch the step without the feature.
+ *       Read-only "stats_samples": runs of the task since the accumulators were last zeroed. */
+int mpas_sigma_stats_configure(mpas_ctx* ctx, int32_t nsigma, const double* sigma);
+int mpas_sigma_stats_reset(mpas_ctx* ctx);
+int mpas_sigma_stats_read(mpas_ctx* ctx, int32_t stat, double* out, int64_t stride_cell, int64_t stride_level);
+int mpas_atm_sigma_stats_accumulate(mpas_ctx* ctx);
 /* rk_timestep.rg:29 summarize_timestep(cr, er, config_print_detailed_minmax_vel,
  *       config_print_global_minmax_vel, config_print_global_minmax_sca): the values the
  *       reference prints, into out[31] (host memory; the call synchronises):

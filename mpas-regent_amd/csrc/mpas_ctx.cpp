@@ -107,7 +107,18 @@ struct mpas_ctx {
     // step, ahead of stage 0's setup; its two tendencies are held over the three stages (as MPAS-A holds its
     // physics tendencies).  0: the step never writes them
     int forcing = 0;
-    int self_on = 1;   // option "self": allow the SELF gathers when the mesh permits
+    // the sigma-level statistics (k_stats.hip; mpas_sigma_stats_configure): the accumulators -- one record of
+    // stats_rec(stats_ns) doubles per local cell, not registry fields -- and the targets with their logs.
+    // Option "stats_every" = N > 0: mpas_atm_srk3 launches the task on the stream after every N-th step since
+    // the option was set (stats_step counts them), behind the step's launches or its replayed graph: never part
+    // of a capture, so the captured step is the one without the option.  stats_samples: the task's runs since
+    // the accumulators were last zeroed
+    double* stats_acc = nullptr;
+    double* stats_sig = nullptr;
+    int stats_ns = 0;
+    int stats_every = 0;
+    int64_t stats_step = 0, stats_samples = 0;
+    int self_on = 1;  // option "self": allow the SELF gathers when the mesh permits
     int self_ok = 0;   // k_prepare's verdict on the uploaded mesh
     int overlap = 1;   // option "overlap": halo exchanges beside interior compute
     // option "hfuse": independent neighbouring kernels share a launch (same values); 2 = on
@@ -1587,6 +1598,29 @@ void srk3_run(mpas_ctx* c, const StepForm& f) {
     c->graph_launches++;
 }
 
+// one sample of the sigma-level statistics (k_stats.hip): the task, under a timing key of its own
+void stats_accumulate(mpas_ctx* c) {
+    if (!c->stats_ns) throw Fail{MPAS_EINVAL, "atm_sigma_stats_accumulate: no sigma levels configured (mpas_sigma_stats_configure)"};
+    if (c->S.physics != 2) throw Fail{MPAS_EINVAL, "atm_sigma_stats_accumulate needs physics = 2 (it samples the MPAS dynamics' state)"};
+    run_task(c, "atm_sigma_stats_accumulate",
+             [&] { return launch_sigma_stats(c->S, c->stream, c->stats_acc, c->stats_sig, c->stats_ns); });
+    c->stats_samples++;
+}
+void stats_zero(mpas_ctx* c) {
+    if (c->stats_acc)
+        hipcheck(hipMemsetAsync(c->stats_acc, 0, (size_t)c->S.nCells * stats_rec(c->stats_ns) * sizeof(double), c->stream),
+                 "hipMemsetAsync");
+    c->stats_samples = 0;
+}
+void stats_free(mpas_ctx* c) {
+    if (c->stats_acc) (void)hipFree(c->stats_acc);
+    if (c->stats_sig) (void)hipFree(c->stats_sig);
+    c->stats_acc = c->stats_sig = nullptr;
+    c->stats_ns = 0;
+    c->stats_every = 0;
+    c->stats_samples = 0;
+}
+
 // one atm_srk3 step, with option stepkeep's bookkeeping: the generation the step runs at, then the one it leaves
 void srk3_step(mpas_ctx* c, double dt, int schedule) {
     const bool act = step_form(c, dt, schedule, 0).stepkeep;
@@ -1600,6 +1634,9 @@ void srk3_step(mpas_ctx* c, double dt, int schedule) {
         c->keep_dt = dt;
         c->keep_schedule = schedule;
     }
+    // option stats_every: the sample behind the step (after its mpas_reconstruct_2d; the substep finish in between
+    // writes nothing the task reads), on the stream and outside the captured graph
+    if (c->stats_every > 0 && ++c->stats_step % c->stats_every == 0) stats_accumulate(c);
 }
 
 // ---- options: one row per name; mpas_set_option and mpas_get_option walk the table ---------------------
@@ -1690,7 +1727,7 @@ const OptRow kOptions[] = {
     opt("physics", &DevState::physics, O_RANGE, 0, 2, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)",
         [](mpas_ctx* c, int64_t& v) {
             if (!v) c->transport = 0;
-            if (v != 2) c->forcing = 0;
+            if (v != 2) c->forcing = 0, c->stats_every = 0;
             c->ett_dirty = true;
         }),
     opt("trorder_e", &DevState::troe, O_RANGE, 0, 1 << 20, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"),
@@ -1721,6 +1758,12 @@ const OptRow kOptions[] = {
             if (v && c->S.physics != 2)
                 throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
         }),
+    opt("stats_every", &mpas_ctx::stats_every, O_RANGE, 0, 0x7fffffff, "stats_every must be >= 0 (steps per sample; 0: none)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (v && (c->S.physics != 2 || !c->stats_ns))
+                throw Fail{MPAS_EINVAL, "stats_every needs physics = 2 and configured sigma levels (mpas_sigma_stats_configure)"};
+            c->stats_step = 0;
+        }),
     opt("overlap", &mpas_ctx::overlap, O_BOOL, 0, 0, nullptr,
         [](mpas_ctx* c, int64_t& v) {
             if (c->halo) c->halo->overlap = (int)v;
@@ -1744,6 +1787,7 @@ const OptRow kOptions[] = {
     query("etile_count", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.ntiles; }),
     query("etile_columns", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.nclo; }),  // closure columns staged per launch
     query("etile_maxclo", [](mpas_ctx* c) -> int64_t { return ett_ensure(c), c->ett.maxclo; }),
+    query("stats_samples", [](mpas_ctx* c) -> int64_t { return c->stats_samples; }),
     query("stepkeep_gen", [](mpas_ctx* c) -> int64_t { return c->keep_gen; }),
     query("dynkeep_fresh", [](mpas_ctx* c) -> int64_t {  // the device flag X_dkf
         int fresh = 0;
@@ -1895,6 +1939,7 @@ int mpas_ctx_destroy(mpas_ctx* c) {
         if (p) (void)hipFree(p);
     if (c->sum_scratch) (void)hipFree(c->sum_scratch);
     if (c->keep_flag) (void)hipFree(c->keep_flag);
+    stats_free(c);
     if (c->sum_out) (void)hipFree(c->sum_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2426,6 +2471,63 @@ int mpas_atm_advance_scalars_mono_rk(mpas_ctx* c, double dt) {
 }
 int mpas_atm_held_suarez_forcing(mpas_ctx* c) {
     MPAS_TASK("atm_held_suarez_forcing", launch_held_suarez_forcing(c->S, c->stream));
+}
+// ---- the sigma-level statistics (k_stats.hip).  None of these calls writes a field or changes the form of the
+// step, so what the step keeps from the one before (guarded's keeps_sml) stays valid
+int mpas_sigma_stats_configure(mpas_ctx* c, int nsigma, const double* sigma) {
+    return guarded(c, [&] {
+        if (nsigma < 0 || nsigma > kStatsMaxSigma || (nsigma && !sigma))
+            throw Fail{MPAS_EINVAL, "mpas_sigma_stats_configure: nsigma must be 0..64"};
+        for (int j = 0; j < nsigma; j++)
+            if (!(sigma[j] > 0.0 && sigma[j] <= 1.0) || (j && !(sigma[j] < sigma[j - 1])))
+                throw Fail{MPAS_EINVAL, "mpas_sigma_stats_configure: sigma levels must lie in (0, 1] and decrease strictly"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        stats_free(c);
+        if (!nsigma) return;
+        double h[2 * kStatsMaxSigma] = {};
+        for (int j = 0; j < nsigma; j++) h[j] = sigma[j], h[kStatsMaxSigma + j] = std::log(sigma[j]);
+        const size_t bytes = (size_t)c->S.nCells * stats_rec(nsigma) * sizeof(double);
+        if (hipMalloc((void**)&c->stats_acc, bytes) != hipSuccess || hipMalloc((void**)&c->stats_sig, sizeof h) != hipSuccess) {
+            (void)hipGetLastError();
+            stats_free(c);
+            throw Fail{MPAS_ENOMEM, "hipMalloc sigma stats"};
+        }
+        c->stats_ns = nsigma;
+        hipcheck(hipMemcpy(c->stats_sig, h, sizeof h, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        stats_zero(c);
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    }, true);
+}
+int mpas_sigma_stats_reset(mpas_ctx* c) {
+    return guarded(c, [&] {
+        if (!c->stats_ns) throw Fail{MPAS_EINVAL, "mpas_sigma_stats_reset: no sigma levels configured"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        stats_zero(c);
+    }, true);
+}
+int mpas_sigma_stats_read(mpas_ctx* c, int stat, double* out, int64_t stride_cell, int64_t stride_level) {
+    return guarded(c, [&] {
+        if (!c->stats_ns) throw Fail{MPAS_EINVAL, "mpas_sigma_stats_read: no sigma levels configured"};
+        if (stat < 0 || stat > kStatsMoments || !out) throw Fail{MPAS_EINVAL, "mpas_sigma_stats_read: stat must be 0..9, out not null"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        const int ns = c->stats_ns, rec = stats_rec(ns), nCO = c->S.nCO;
+        const int off = stat * ns, cnt = stat == kStatsMoments ? 3 : ns;
+        std::vector<double> h((size_t)nCO * rec);
+        if (nCO)
+            hipcheck(hipMemcpyAsync(h.data(), c->stats_acc, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream),
+                     "hipMemcpyAsync D2H");
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        for (int e = 0; e < nCO; e++)
+            for (int j = 0; j < cnt; j++)
+                *(double*)((char*)out + e * stride_cell + j * stride_level) = h[(size_t)e * rec + off + j];
+    }, true);
+}
+int mpas_atm_sigma_stats_accumulate(mpas_ctx* c) {
+    return guarded(c, [&] {
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        stats_accumulate(c);
+    }, true);
 }
 int mpas_atm_compute_output_diagnostics(mpas_ctx* c) {
     MPAS_TASK("atm_compute_output_diagnostics", launch_output_diagnostics(c->S, c->stream));

@@ -387,6 +387,13 @@ hipError_t launch_advance_scalars(const DevState& S, hipStream_t st, double dt);
 hipError_t launch_advance_scalars_mono_rk(const DevState& S, hipStream_t st, double dt);
 // the Held-Suarez forcing (k_forcing.hip; the MPAS dynamics): tend_rtheta_physics, tend_ru_physics
 hipError_t launch_held_suarez_forcing(const DevState& S, hipStream_t st);
+// the sigma-level statistics (k_stats.hip; the MPAS dynamics): one sample of every owned cell column added to
+// the accumulators.  acc: per cell one record of `rec` doubles (stats_rec) -- the nine moments n, u, v, T, uu,
+// vv, TT, uv, vT as runs of nsigma, then [sum ps, sum ps^2, calls]; sig: the nsigma targets, then their logs
+constexpr int kStatsMaxSigma = 64;
+constexpr int kStatsMoments = 9;
+inline int stats_rec(int nsigma) { return (kStatsMoments * nsigma + 3 + 15) / 16 * 16; }  // (whole 128-B lines)
+hipError_t launch_sigma_stats(const DevState& S, hipStream_t st, double* acc, const double* sig, int nsigma);
 hipError_t launch_damping_coefs(const DevState& S, hipStream_t st, double zd, double xnutr);
 hipError_t launch_compute_signs(const DevState& S, hipStream_t st);
 // strided device view <-> LP-padded 3-D field (elem 8: fp64, 1: uint8 masks)

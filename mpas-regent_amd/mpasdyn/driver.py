@@ -6,6 +6,8 @@ state -> atm_core_init's one-time precompute -> time steps -> atm_compute_output
                              [--schedule 1] [--physics {0,1,2}] [--transport] [--day]
                              [--transport-scheme {single,rk3}] [--out timestep_output.nc]
                              [--forcing held-suarez] [--days N]
+                             [--stats OUT.npz] [--stats-every N] [--stats-after-days D]
+                             [--sigma-levels S0,S1,...] [--stats-bands B]
 
 Without --grid the reference's own x1.2562 mesh (tests/golden fixture) is used.  The mesh
 is taken in mpas-mode (0-based) ids, the ids the JW state (mpasdyn/jw.py) is defined on.
@@ -22,7 +24,14 @@ MPAS-A's three-stage RK3 (option "transport" = 2, include/mpas_dyn.h).  `--forci
 (implies `--physics 2`) runs the Held-Suarez forcing in every step (option "forcing" = 1): Newtonian
 relaxation of temperature and boundary-layer friction, the long forced integration of a dry core;
 the final report then also gives the global mean temperature of the lowest level and the largest
-|uReconstructZonal|.  `--days N` sets the steps to N simulated days."""
+|uReconstructZonal|.  `--days N` sets the steps to N simulated days.  `--stats OUT.npz` (needs the MPAS
+dynamics: `--physics 2` or `--forcing`) accumulates time-mean statistics on sigma levels on the device
+(include/mpas_dyn.h, mpas_atm_sigma_stats_accumulate): a sample after every `--stats-every`-th step (default
+1) at the levels `--sigma-levels` (default 0.975, 0.925, ..., 0.025), zeroed once more after
+`--stats-after-days` D simulated days of spin-up; after the last step mpasdyn.stats.zonal_means turns them
+into `--stats-bands` latitude bands (default 36) of [u], [v], [T], [ps] and the eddy terms, written to
+OUT.npz, and one line reports the largest [u] with its latitude and sigma and the range of [T] at the lowest
+sampled level."""
 import argparse
 import os
 import sys
@@ -31,13 +40,15 @@ import numpy as np
 
 
 def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=False, out=None, device=0,
-        log=print, forcing=None):
+        log=print, forcing=None, stats=None, stats_every=1, stats_after_days=0.0, sigma_levels=None, stats_bands=36):
     """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport;
-    forcing: None or "held-suarez" (the MPAS dynamics: physics becomes 2)"""
+    forcing: None or "held-suarez" (the MPAS dynamics: physics becomes 2);
+    stats: None or the .npz path the zonal-mean sigma-level statistics are written to (physics 2)"""
     from . import build_state as bs
     from . import jw, lib
     from . import mesh as M
     from . import tasks as T
+    from .stats import DEFAULT_SIGMA, zonal_means
     if np.asarray(m.cellsOnEdge).min() != 0:
         m = M.zero_based(m)
     st = bs.build_state(m, L, "physical", vertical=False)
@@ -45,6 +56,11 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
     if forcing not in (None, "held-suarez"):
         raise ValueError(f"unknown forcing {forcing!r}")
     physics = 2 if forcing else int(physics) if physics else (1 if transport else 0)
+    if stats and physics != 2:
+        raise ValueError("--stats needs the MPAS dynamics (--physics 2 or --forcing held-suarez)")
+    sigma = list(sigma_levels) if sigma_levels is not None else list(DEFAULT_SIGMA)
+    reset_at = int(round(stats_after_days * 86400.0 / dt)) if stats else -1
+    acc = None
     nC = m.nCells
     vol = 1.0 / (st["invAreaCell"][:nC, 0][:, None] * st["rdzw"][:L][None, :])
     mass0 = float(np.sum(st["rho_zz"][:nC, :L] * vol))
@@ -57,13 +73,22 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         if physics == 2:  # MPAS-A's atm_core_init diagnostics of the initial state
             T.atm_compute_solve_diagnostics(ctx, False, -1)
             T.mpas_reconstruct_2d(ctx, False, True)
+        if stats:
+            T.sigma_stats_configure(ctx, sigma)
+            ctx.set_option("stats_every", stats_every)
         for j in range(steps):
+            if j == reset_at and j > 0:  # the spin-up is over: from zero, the step count too
+                T.sigma_stats_reset(ctx)
+                ctx.set_option("stats_every", stats_every)
             T.atm_do_timestep(ctx, float(j) if dt_from_step else dt) if schedule == 0 else \
                 T.atm_srk3(ctx, float(j) if dt_from_step else dt, schedule)
             s = T.summarize_timestep(ctx, False, True)
             log(f"step {j}: w in [{s[27]:.6g}, {s[28]:.6g}]  u in [{s[29]:.6g}, {s[30]:.6g}]")
         T.atm_compute_output_diagnostics(ctx)
         ctx.sync()
+        if stats:
+            acc = T.sigma_stats_read(ctx)
+            samples = ctx.get_option("stats_samples")
         ctx.download(st)
     if physics == 2:
         sp = st["surface_pressure"][:nC, 0] / 100.0
@@ -76,6 +101,17 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         uz = np.abs(st["uReconstructZonal"][:nC, :L])
         log(f"{forcing}: lowest-level temperature mean {float(np.sum(t0 * area) / np.sum(area)):.4f} K; "
             f"max |uReconstructZonal| {float(uz.max()):.4f} m/s")
+    if stats:
+        z = zonal_means(acc, st["lat"][:nC, 0], 1.0 / st["invAreaCell"][:nC, 0], stats_bands)
+        np.savez(stats, sigma=np.array(sigma), samples=samples, **z)
+        if np.isfinite(z["u"]).any():
+            b, jm = np.unravel_index(np.nanargmax(z["u"]), z["u"].shape)
+            low = int(np.nonzero(np.isfinite(z["T"]).any(axis=0))[0][0])  # (the levels decrease: the first sampled one)
+            log(f"stats: {samples} samples; max [u] {z['u'][b, jm]:.4f} m/s at {np.degrees(z['lat'][b]):.1f} deg, sigma "
+                f"{sigma[jm]:g}; [T] at sigma {sigma[low]:g} in [{np.nanmin(z['T'][:, low]):.4f}, "
+                f"{np.nanmax(z['T'][:, low]):.4f}] K -> {stats}")
+        else:
+            log(f"stats: {samples} samples, no sigma level sampled -> {stats}")
     if out:
         from .meshio import write_output_plotting
         write_output_plotting(out, m, st)
@@ -99,6 +135,12 @@ def main(argv=None):
                     help="held-suarez: Newtonian relaxation and boundary-layer friction in every step (implies --physics 2)")
     ap.add_argument("--days", type=float, default=None, help="N simulated days: steps = N 86400 / dt")
     ap.add_argument("--out", default="timestep_output.nc")
+    ap.add_argument("--stats", default=None, metavar="OUT.npz",
+                    help="time-mean zonal means and eddy terms on sigma levels, written after the last step")
+    ap.add_argument("--stats-every", type=int, default=1, help="steps per sample")
+    ap.add_argument("--stats-after-days", type=float, default=0.0, help="spin-up: the accumulators are zeroed after D days")
+    ap.add_argument("--sigma-levels", default=None, help="comma-separated, in (0, 1], decreasing (default 0.975, ..., 0.025)")
+    ap.add_argument("--stats-bands", type=int, default=36, help="latitude bands of the zonal means")
     a = ap.parse_args(argv)
     from . import mesh as M
     if a.grid:
@@ -110,7 +152,10 @@ def main(argv=None):
     if a.days is not None:
         steps = int(round(a.days * 86400.0 / a.dt))
     transport = (2 if a.transport_scheme == "rk3" else 1) if a.transport else 0
-    run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out, forcing=a.forcing)
+    sigma = [float(x) for x in a.sigma_levels.split(",")] if a.sigma_levels else None
+    run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out, forcing=a.forcing,
+        stats=a.stats, stats_every=a.stats_every, stats_after_days=a.stats_after_days, sigma_levels=sigma,
+        stats_bands=a.stats_bands)
     return 0
 
 

@@ -261,6 +261,11 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
         # cell kernel stores and the edge kernel gathers (X_hskv) takes no credit, as every scratch
         return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "lat", "ru", "cellsOnEdge"],
                 ["tend_rtheta_physics", "tend_ru_physics"])
+    if task == "atm_sigma_stats_accumulate":  # k_stats.hip (option stats_every; no reference task)
+        # eight C3 columns read, no field written; the accumulators are not registry fields: b_alg adds them
+        # (stats_acc_bytes) -- they are state, read and written once per sample, not scratch
+        return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "uReconstructZonal",
+                 "uReconstructMeridional", "rdzw"], [])
     if task in ("stepkeep_restore_w", "stepkeep_save_w"):  # option stepkeep = 2 (no reference task)
         # one cell column read, one written: w from (to) the scratch copy of the w stage 0's dyn_tend leaves
         return ["w"], ["w"]
@@ -294,9 +299,18 @@ SLOT_FIELDS = {"zb_cell", "zb3_cell"}
 SLOTS_READ = 6
 
 
-def b_alg(task, dims, **kw):
-    """algorithmic bytes of one launch of `task` at dims = (nCells, nEdges, nVertices, L)"""
+def stats_acc_bytes(nCells, nsigma):
+    """the sigma-level statistics' accumulators: nine moments per (cell, target) and [sum ps, sum ps^2, calls]
+    per cell, fp64"""
+    return 8 * nCells * (9 * nsigma + 3)
+
+
+def b_alg(task, dims, nsigma=20, **kw):
+    """algorithmic bytes of one launch of `task` at dims = (nCells, nEdges, nVertices, L)
+    (nsigma: the configured targets of atm_sigma_stats_accumulate, whose accumulators are read and written)"""
     reads, writes = _sets(task, **kw)
+    if task == "atm_sigma_stats_accumulate":
+        return sum(field_bytes(x, *dims) for x in reads) + 2 * stats_acc_bytes(dims[0], nsigma)
 
     def fb(x):
         b = field_bytes(x, *dims)

@@ -157,6 +157,42 @@ def atm_held_suarez_forcing(ctx):
     ctx._check(ctx.lib.mpas_atm_held_suarez_forcing(ctx.h), "atm_held_suarez_forcing")
 
 
+# ---- time-mean statistics on sigma levels (k_stats.hip; include/mpas_dyn.h, restated by tests/stats_ref.py)
+STATS = ("n", "u", "v", "T", "uu", "vv", "TT", "uv", "vT")  # mpas_sigma_stats_read's stat 0..8; 9: "ps"
+
+
+def sigma_stats_configure(ctx, sigma):
+    """allocate and zero the accumulators for the targets `sigma` (in (0, 1], strictly decreasing, at
+    most 64); an empty list frees them"""
+    import numpy as np
+    s = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+    ctx._check(ctx.lib.mpas_sigma_stats_configure(ctx.h, len(s), s.ctypes.data), "sigma_stats_configure")
+    ctx._stats_ns = len(s)
+
+
+def sigma_stats_reset(ctx):
+    ctx._check(ctx.lib.mpas_sigma_stats_reset(ctx.h), "sigma_stats_reset")
+
+
+def atm_sigma_stats_accumulate(ctx):
+    """one sample of the state as found, added to the accumulators of every owned cell"""
+    ctx._check(ctx.lib.mpas_atm_sigma_stats_accumulate(ctx.h), "atm_sigma_stats_accumulate")
+
+
+def sigma_stats_read(ctx, n_owned=None):
+    """the accumulators of the owned cells (the first n_owned local cells; default: all): a dict of
+    [n_owned, nsigma] arrays under the names of STATS, and "ps" [n_owned, 3] = sum ps, sum ps^2, calls"""
+    import numpy as np
+    n = ctx.dims[0] if n_owned is None else int(n_owned)
+    out = {}
+    for i, name in enumerate(STATS + ("ps",)):
+        a = np.zeros((n, 3 if name == "ps" else ctx._stats_ns))
+        ctx._check(ctx.lib.mpas_sigma_stats_read(ctx.h, i, a.ctypes.data, a.strides[0], a.strides[1]),
+                   f"sigma_stats_read {name}")
+        out[name] = a
+    return out
+
+
 def summarize_timestep(ctx, config_print_detailed_minmax_vel=False, config_print_global_minmax_vel=False,
                        config_print_global_minmax_sca=False):
     """rk_timestep.rg:29; returns the 31 values the reference prints (layout: include/mpas_dyn.h)"""

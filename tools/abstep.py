@@ -3,7 +3,7 @@
 K atm_srk3 steps (HIP graph replay, as bench.py times them) under each option set (options a variant does not name at their defaults); per
 variant the median per-step device time over all rounds (HIP events between steps).
 
-usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport]
+usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport] [--sigma-levels N]
        --variants "fusesetup=1" "fusesetup=0"
 """
 import argparse
@@ -29,12 +29,16 @@ def main():
     ap.add_argument("--variants", nargs="+", required=True)
     ap.add_argument("--physics", type=int, default=0, choices=[0, 1, 2])
     ap.add_argument("--transport", action="store_true", help="physics 1 + the scalar transport (bench --transport)")
+    ap.add_argument("--sigma-levels", type=int, default=0,
+                    help="configure N sigma targets of the sigma-level statistics (physics 2): stats_every usable")
     a = ap.parse_args()
     physics = max(a.physics, 1 if a.transport else 0)
     m, st = bench.build_inputs(a.ncells, a.levels, zero_based=physics)
     ctx = lib.Context(m.nCells, m.nEdges, m.nVertices, a.levels)
     ctx.set_option("physics", physics)
     ctx.set_option("transport", int(a.transport))
+    if a.sigma_levels:  # N targets evenly spaced in (0, 1): 0.975, 0.925, ... at N = 20
+        T.sigma_stats_configure(ctx, [1.0 - (j + 0.5) / a.sigma_levels for j in range(a.sigma_levels)])
     bench.upload_inputs(ctx, st)
     dt = bench.dt_for(a.ncells)
     hip = bench.Hip()

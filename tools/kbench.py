@@ -4,7 +4,10 @@ workload once and runs interleaved rounds of full RK3 steps under each option se
 reporting the median per-task device time (HIP events on the task stream).
 
 usage: python tools/kbench.py [--ncells 163842] [--levels 56] [--rounds 5] [--physics N] [--transport]
-       --variants "xcd=1" "xcd=0"
+       [--sigma-levels N] --variants "xcd=1" "xcd=0"
+
+--sigma-levels N (physics 2) configures N sigma targets of the sigma-level statistics first (the driver's
+default list at 20), so that a variant may set stats_every=1 and the task's row appears.
 """
 import argparse
 import json
@@ -28,12 +31,15 @@ def main():
     ap.add_argument("--variants", nargs="+", default=["xcd=1", "xcd=0"])
     ap.add_argument("--physics", type=int, default=0)
     ap.add_argument("--transport", action="store_true", help="physics 1 + the scalar transport (bench --transport)")
+    ap.add_argument("--sigma-levels", type=int, default=0, help="configure N sigma targets (physics 2): stats_every usable")
     a = ap.parse_args()
     physics = max(a.physics, 1 if a.transport else 0)
     m, st = bench.build_inputs(a.ncells, a.levels, zero_based=physics)
     ctx = lib.Context(m.nCells, m.nEdges, m.nVertices, a.levels)
     ctx.set_option("physics", physics)
     ctx.set_option("transport", int(a.transport))
+    if a.sigma_levels:  # N targets evenly spaced in (0, 1): 0.975, 0.925, ... at N = 20
+        T.sigma_stats_configure(ctx, [1.0 - (j + 0.5) / a.sigma_levels for j in range(a.sigma_levels)])
     bench.upload_inputs(ctx, st)
     dt = bench.dt_for(a.ncells)
     T.atm_srk3(ctx, dt, 1)
