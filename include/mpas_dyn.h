@@ -406,6 +406,57 @@ int mpas_sigma_stats_configure(mpas_ctx* ctx, int32_t nsigma, const double* sigm
 int mpas_sigma_stats_reset(mpas_ctx* ctx);
 int mpas_sigma_stats_read(mpas_ctx* ctx, int32_t stat, double* out, int64_t stride_cell, int64_t stride_level);
 int mpas_atm_sigma_stats_accumulate(mpas_ctx* ctx);
+/* Kessler warm-rain microphysics (k_kessler.hip) in the form of the DCMIP-2016 moist test cases (Klemp et al.
+ *       2015): the first writer of rt_diabatic_tend and the first reader of the transported scalars.  No reference
+ *       entry point ("physics" = 2, else MPAS_EINVAL; dt > 0).  Scalars 0, 1, 2 are qv, qc, qr (kg/kg).  Per owned
+ *       cell column, levels k = 0..L-1 (L = nVertLevels, 0 the lowest), every input as found:
+ *         rho_d = zz rho_zz;   m = rho_zz / rdzw (layer mass, kg/m2: the metric the transport conserves)
+ *         dz = 1 / (rdzw zz);  pi = exner, held fixed over the call;   rvord = 461.6 / 287
+ *         theta = theta_m / (1 + rvord qv);   T = pi theta (from the current theta in every subcycle)
+ *       constants f2x = 17.27, Lv = 2.5e6, cp = 1003, f5 = 237.3 f2x Lv / cp, xk = 0.2875, psl = 1000:
+ *         r = 0.001 rho_d;   pc = 3.8 / (pi^(1/xk) psl);   vt = 36.34 (qr r)^0.1364 sqrt(rho_d(0) / rho_d)
+ *         x = max_k vt(k) dt / (0.8 dz(k));   n = max(1, ceil(x)) (at most 4096);   dt0 = dt / n
+ *       n is the column's and fixed for the call; vt is formed again before every subcycle but the first.  One
+ *       subcycle, a finite-volume sedimentation on the model's layers, then the DCMIP scheme's sources:
+ *         F(k) = rho_d qr vt, F(L) = 0;   P += dt0 F(0) (kg/m2 = mm);   sed = dt0 (F(k+1) - F(k)) / m
+ *         qrprod = qc - (qc - dt0 max(0.001 (qc - 0.001), 0)) / (1 + dt0 2.2 qr^0.875)
+ *         qc = max(qc - qrprod, 0);   qr = max(qr + qrprod + sed, 0)
+ *         qvs = pc exp(f2x (T - 273) / (T - 36));   prod = (qv - qvs) / (1 + qvs f5 / (T - 36)^2)
+ *         ern = min(dt0 ((1.6 + 124.9 (r qr)^0.2046) (r qr)^0.525 / (2.55e6 pc / (3.8 qvs) + 5.4e5))
+ *                   max(qvs - qv, 0) / (r qvs),  max(-prod - qc, 0),  qr)
+ *         cond = max(prod, -qc);   theta += Lv / (cp pi) (cond - ern)
+ *         qv = max(qv - cond + ern, 0);   qc += cond;   qr -= ern
+ *       The powers of r qr are exp(a log(r qr)) on one logarithm per evaluation point, taken as -inf (every
+ *       power 0) where r qr <= 0 -- a rain the transport's limiter left a rounding below zero gives no NaN and
+ *       the subcycle's max(., 0) lifts it; qr^0.875 = exp(0.875 (log(r qr) - log r)); max and min are selects on
+ *       > and <.  Written, with theta', qv' the values
+ *       after the last subcycle:
+ *         theta_m' = theta_m + (theta' - theta)(1 + rvord qv') + theta rvord (qv' - qv)
+ *         rt_diabatic_tend = (theta_m' - theta_m) / dt;   rtheta_p' = rtheta_p + rho_zz (theta_m' - theta_m)
+ *         exner, pressure_p from rtheta_p' by atm_recover_large_step_variables_work's two expressions (MPAS form)
+ *         scalars 0, 1, 2
+ *       and no other field (rho_zz is not written; scalars 3..7, level nVertLevels and the zero slot keep their
+ *       bits).  The increment forms are deliberate: a cell in which no subcycle had a non-zero cond or ern keeps
+ *       theta_m, rtheta_p, qv and qc bit for bit and gets rt_diabatic_tend = +0.0.  Contract: rdzw, zz > 0, T > 36,
+ *       qv, qc, qr >= 0, x < 4096; any other input leaves the result undefined, but the call still writes only its
+ *       own fields.  Statement order: tests/kessler_ref.py (device pow / exp / log against the host's are the only
+ *       differences).  A decomposed context runs its owned cells; no gather, the written fields' ghosts go stale.
+ *       Per owned cell three accumulators, plain `+=` in call order, one writer each (two runs give the same
+ *       bits): 0 the accumulated rain P (mm), 1 the last call's P, 2 the number of calls (as a double).  They are
+ *       not registry fields (mpas_field_count is unchanged) and are allocated, zeroed, on first use.
+ * mpas_precip_read copies accumulator `which` (0..2) of the owned cells to out (the call synchronises): cell e at
+ *       byte offset e*stride_cell.  mpas_precip_reset zeroes all three.
+ * Option "microphysics" = 1 (needs "physics" = 2, else MPAS_EINVAL; a value other than 0 or 1: MPAS_EINVAL;
+ *       default 0; reset to 0 when "physics" leaves 2) makes mpas_atm_srk3 end every step with the task over the
+ *       step's dt: behind the transport, mpas_reconstruct_2d and the substep finish, ahead of a "stats_every"
+ *       sample, inside the captured graph, under the timing key "atm_kessler_microphysics".  With 0 the step is
+ *       launch for launch the step without the feature.  It does not require "transport" (the driver pairs them).
+ *       The dynamics do not yet feel water loading (qtot, cqw, cqu stay atm_compute_moist_coefficients' constants).
+ *       "forcing" and "stats_every" combine with it unchanged: their T = theta_m exner is then the virtual
+ *       temperature. */
+int mpas_atm_kessler_microphysics(mpas_ctx* ctx, double dt);
+int mpas_precip_read(mpas_ctx* ctx, int32_t which, double* out, int64_t stride_cell);
+int mpas_precip_reset(mpas_ctx* ctx);
 /* rk_timestep.rg:29 summarize_timestep(cr, er, config_print_detailed_minmax_vel,
  *       config_print_global_minmax_vel, config_print_global_minmax_sca): the values the
  *       reference prints, into out[31] (host memory; the call synchronises):

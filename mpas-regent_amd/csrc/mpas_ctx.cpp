@@ -118,6 +118,13 @@ struct mpas_ctx {
     int stats_ns = 0;
     int stats_every = 0;
     int64_t stats_step = 0, stats_samples = 0;
+    // option "microphysics" (the MPAS dynamics, physics = 2): 1 -- atm_srk3 ends with the Kessler warm-rain task
+    // (k_kessler.hip) over the step's dt, inside the captured graph; 0: the step is launch for launch the step
+    // without it.  precip: the task's accumulators -- three runs of nCells doubles (accumulated rain, the last
+    // call's, the calls), not registry fields -- allocated and zeroed on first use (precip_ensure: when the option
+    // is set, or at the first direct call; never inside a capture)
+    int microphysics = 0;
+    double* precip = nullptr;
     int self_on = 1;  // option "self": allow the SELF gathers when the mesh permits
     int self_ok = 0;   // k_prepare's verdict on the uploaded mesh
     int overlap = 1;   // option "overlap": halo exchanges beside interior compute
@@ -344,7 +351,9 @@ const int kKeepL[] = {
     // mpas_reconstruct_2d
     F_uReconstructX, F_uReconstructY, F_uReconstructZ, F_uReconstructZonal, F_uReconstructMeridional,
     // the Held-Suarez forcing
-    F_tend_rtheta_physics, F_tend_ru_physics};
+    F_tend_rtheta_physics, F_tend_ru_physics,
+    // the Kessler microphysics (its other fields: recover's)
+    F_rt_diabatic_tend};
 const int kKeep0[] = {F_cofwr, F_cofwz, F_a_tri, F_b_tri, F_c_tri, F_alpha_tri, F_cqw, F_rw};
 int keep_kind(int f) { return kFields[f].kind == K_C3 ? 0 : kFields[f].kind == K_E3 ? 1 : 2; }  // KC / KE / KV
 
@@ -1114,7 +1123,7 @@ StepForm step_form(const mpas_ctx* c, double dt, int schedule, int gen) {
     // option stepkeep: the step whose launches the kept generation may thin out -- the headline's order
     // (DESIGN.md §4k lists why each condition is there); anywhere else keep_gen stays 0
     f.stepkeep = c->stepkeep && f.keep && c->ntu == 1 && c->defer4 && f.fcopy && c->accoef && !f.hf && !c->tmedge &&
-                 !c->etile && !c->transport && !c->forcing && f.rk_of[0] == 0 && f.rk_of[1] != 0 && f.rk_of[2] != 0;
+                 !c->etile && !c->transport && !c->forcing && !c->microphysics && f.rk_of[0] == 0 && f.rk_of[1] != 0 && f.rk_of[2] != 0;
     // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
     f.vik = c->vikeep && f.stepkeep;
     // option a0keep: a full step leaves the next step's kdiff in X_kd0; a kept step takes it from there and runs
@@ -1459,6 +1468,10 @@ void step_end(mpas_ctx* c, const StepForm& f, StepRun& r) {
             return launch_substep_finish(S, st, 1, f.dynamics_split, f.norz ? 1 : 0, f.a0k && f.kept ? 1 : 0);
         });
     r.fb.finish();
+    // option microphysics: the step ends with the Kessler task on the state the step leaves -- behind the transport
+    // and the reconstruction; its rt_diabatic_tend is the heating of the next step's dynamics
+    if (c->microphysics)
+        run_task(c, "atm_kessler_microphysics", [&] { return launch_kessler(S, st, dt, c->precip); });
     // :492 summarize_timestep(cr, er, false, false, false) (constants.rg:67-69): prints only
 }
 
@@ -1621,6 +1634,19 @@ void stats_free(mpas_ctx* c) {
     c->stats_samples = 0;
 }
 
+// the Kessler task's accumulators (mpas_ctx::precip), allocated and zeroed on first use
+void precip_ensure(mpas_ctx* c) {
+    if (c->precip) return;
+    const size_t bytes = 3 * (size_t)c->S.nCells * sizeof(double);
+    if (hipMalloc((void**)&c->precip, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->precip = nullptr;
+        throw Fail{MPAS_ENOMEM, "hipMalloc precipitation accumulators"};
+    }
+    hipcheck(hipMemsetAsync(c->precip, 0, bytes, c->stream), "hipMemsetAsync");
+    hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+}
+
 // one atm_srk3 step, with option stepkeep's bookkeeping: the generation the step runs at, then the one it leaves
 void srk3_step(mpas_ctx* c, double dt, int schedule) {
     const bool act = step_form(c, dt, schedule, 0).stepkeep;
@@ -1727,7 +1753,7 @@ const OptRow kOptions[] = {
     opt("physics", &DevState::physics, O_RANGE, 0, 2, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)",
         [](mpas_ctx* c, int64_t& v) {
             if (!v) c->transport = 0;
-            if (v != 2) c->forcing = 0, c->stats_every = 0;
+            if (v != 2) c->forcing = 0, c->stats_every = 0, c->microphysics = 0;
             c->ett_dirty = true;
         }),
     opt("trorder_e", &DevState::troe, O_RANGE, 0, 1 << 20, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"),
@@ -1757,6 +1783,15 @@ const OptRow kOptions[] = {
         [](mpas_ctx* c, int64_t& v) {
             if (v && c->S.physics != 2)
                 throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
+        }),
+    opt("microphysics", &mpas_ctx::microphysics, O_RANGE, 0, 1, "microphysics must be 0 or 1 (Kessler warm rain)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (v && c->S.physics != 2)
+                throw Fail{MPAS_EINVAL, "microphysics needs physics = 2 (the MPAS forms consume rt_diabatic_tend)"};
+            if (v) {
+                hipcheck(hipSetDevice(c->device), "hipSetDevice");
+                precip_ensure(c);
+            }
         }),
     opt("stats_every", &mpas_ctx::stats_every, O_RANGE, 0, 0x7fffffff, "stats_every must be >= 0 (steps per sample; 0: none)",
         [](mpas_ctx* c, int64_t& v) {
@@ -1940,6 +1975,7 @@ int mpas_ctx_destroy(mpas_ctx* c) {
     if (c->sum_scratch) (void)hipFree(c->sum_scratch);
     if (c->keep_flag) (void)hipFree(c->keep_flag);
     stats_free(c);
+    if (c->precip) (void)hipFree(c->precip);
     if (c->sum_out) (void)hipFree(c->sum_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2471,6 +2507,38 @@ int mpas_atm_advance_scalars_mono_rk(mpas_ctx* c, double dt) {
 }
 int mpas_atm_held_suarez_forcing(mpas_ctx* c) {
     MPAS_TASK("atm_held_suarez_forcing", launch_held_suarez_forcing(c->S, c->stream));
+}
+// ---- the Kessler microphysics (k_kessler.hip): the task (a field-writing call like any other), and its
+// accumulators, which are no fields (reading or zeroing them leaves what the step keeps as it is)
+int mpas_atm_kessler_microphysics(mpas_ctx* c, double dt) {
+    return guarded(c, [&] {
+        if (c->S.physics != 2) throw Fail{MPAS_EINVAL, "atm_kessler_microphysics needs physics = 2 (the MPAS dynamics' state)"};
+        if (!(dt > 0.0)) throw Fail{MPAS_EINVAL, "atm_kessler_microphysics: dt must be positive"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        precip_ensure(c);
+        run_task(c, "atm_kessler_microphysics", [&] { return launch_kessler(c->S, c->stream, dt, c->precip); });
+    });
+}
+int mpas_precip_read(mpas_ctx* c, int which, double* out, int64_t stride_cell) {
+    return guarded(c, [&] {
+        if (which < 0 || which > 2 || !out) throw Fail{MPAS_EINVAL, "mpas_precip_read: which must be 0..2, out not null"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        precip_ensure(c);
+        const int nCO = c->S.nCO;
+        std::vector<double> h((size_t)nCO);
+        if (nCO)
+            hipcheck(hipMemcpyAsync(h.data(), c->precip + (size_t)which * c->S.nCells, h.size() * sizeof(double),
+                                    hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync D2H");
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        for (int e = 0; e < nCO; e++) *(double*)((char*)out + e * stride_cell) = h[(size_t)e];
+    }, true);
+}
+int mpas_precip_reset(mpas_ctx* c) {
+    return guarded(c, [&] {
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        precip_ensure(c);
+        hipcheck(hipMemsetAsync(c->precip, 0, 3 * (size_t)c->S.nCells * sizeof(double), c->stream), "hipMemsetAsync");
+    }, true);
 }
 // ---- the sigma-level statistics (k_stats.hip).  None of these calls writes a field or changes the form of the
 // step, so what the step keeps from the one before (guarded's keeps_sml) stays valid

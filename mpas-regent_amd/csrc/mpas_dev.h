@@ -394,6 +394,17 @@ constexpr int kStatsMaxSigma = 64;
 constexpr int kStatsMoments = 9;
 inline int stats_rec(int nsigma) { return (kStatsMoments * nsigma + 3 + 15) / 16 * 16; }  // (whole 128-B lines)
 hipError_t launch_sigma_stats(const DevState& S, hipStream_t st, double* acc, const double* sig, int nsigma);
+// Kessler warm-rain microphysics (k_kessler.hip; the MPAS dynamics; identical to tests/kessler_ref.py): theta_m,
+// rtheta_p, exner, pressure_p, rt_diabatic_tend and scalars 0..2 of the owned cells.  precip: three runs of nCells
+// doubles -- accumulated rain (mm), the last call's, the number of calls -- not registry fields
+constexpr double kKsRv = 461.6;      // gas constant of water vapour: rvord = kKsRv / kRgas
+constexpr double kKsF2x = 17.27;
+constexpr double kKsLv = 2.5e6;      // latent heat of vaporisation, as published with the scheme
+constexpr double kKsCp = 1003.0;     // the scheme's own cp (not kCp)
+constexpr double kKsXk = 0.2875;
+constexpr double kKsPsl = 1000.0;    // hPa
+constexpr int kKsMaxSub = 4096;      // most sedimentation subcycles of a call (never reached inside the contract)
+hipError_t launch_kessler(const DevState& S, hipStream_t st, double dt, double* precip);
 hipError_t launch_damping_coefs(const DevState& S, hipStream_t st, double zd, double xnutr);
 hipError_t launch_compute_signs(const DevState& S, hipStream_t st);
 // strided device view <-> LP-padded 3-D field (elem 8: fp64, 1: uint8 masks)

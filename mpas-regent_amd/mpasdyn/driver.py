@@ -8,6 +8,7 @@ state -> atm_core_init's one-time precompute -> time steps -> atm_compute_output
                              [--forcing held-suarez] [--days N]
                              [--stats OUT.npz] [--stats-every N] [--stats-after-days D]
                              [--sigma-levels S0,S1,...] [--stats-bands B]
+                             [--microphysics kessler]
 
 Without --grid the reference's own x1.2562 mesh (tests/golden fixture) is used.  The mesh
 is taken in mpas-mode (0-based) ids, the ids the JW state (mpasdyn/jw.py) is defined on.
@@ -31,7 +32,14 @@ dynamics: `--physics 2` or `--forcing`) accumulates time-mean statistics on sigm
 `--stats-after-days` D simulated days of spin-up; after the last step mpasdyn.stats.zonal_means turns them
 into `--stats-bands` latitude bands (default 36) of [u], [v], [T], [ps] and the eddy terms, written to
 OUT.npz, and one line reports the largest [u] with its latitude and sigma and the range of [T] at the lowest
-sampled level."""
+sampled level.  `--microphysics kessler` (needs `--physics 2`; implies `--transport --transport-scheme rk3`)
+runs the moist baroclinic wave of DCMIP-2016: mpasdyn.jw.add_moisture puts the analytic humidity on the JW state
+(here with the test case's zonal-wind perturbation, so that the wave grows),
+rt_diabatic_tend starts at 0, and every step ends with the Kessler warm-rain task (option "microphysics" = 1,
+include/mpas_dyn.h).  The final report gives the accumulated precipitation (min / max / area mean, mm) and the
+water budget sum(area m (qv + qc + qr)) + sum(area rain) relative to its initial value; the accumulated rain goes
+into the output file as `rain`.  The dynamics do not yet feel water loading, and the log says so: a smoke run,
+not a validation of the DCMIP case."""
 import argparse
 import os
 import sys
@@ -40,22 +48,37 @@ import numpy as np
 
 
 def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=False, out=None, device=0,
-        log=print, forcing=None, stats=None, stats_every=1, stats_after_days=0.0, sigma_levels=None, stats_bands=36):
+        log=print, forcing=None, stats=None, stats_every=1, stats_after_days=0.0, sigma_levels=None, stats_bands=36,
+        microphysics=None):
     """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport;
     forcing: None or "held-suarez" (the MPAS dynamics: physics becomes 2);
-    stats: None or the .npz path the zonal-mean sigma-level statistics are written to (physics 2)"""
+    stats: None or the .npz path the zonal-mean sigma-level statistics are written to (physics 2);
+    microphysics: None or "kessler" (needs physics 2; the RK3 transport and the moist JW state with it)"""
     from . import build_state as bs
-    from . import jw, lib
+    from . import jw, lib, moist
     from . import mesh as M
     from . import tasks as T
     from .stats import DEFAULT_SIGMA, zonal_means
     if np.asarray(m.cellsOnEdge).min() != 0:
         m = M.zero_based(m)
     st = bs.build_state(m, L, "physical", vertical=False)
-    jw.init_atm_case_jw(m, st)
+    # (the moist run is the baroclinic wave: with the test case's zonal-wind perturbation, which the dry runs leave out)
+    jw.init_atm_case_jw(m, st, perturb=bool(microphysics))
     if forcing not in (None, "held-suarez"):
         raise ValueError(f"unknown forcing {forcing!r}")
+    if microphysics not in (None, "kessler"):
+        raise ValueError(f"unknown microphysics {microphysics!r}")
+    if microphysics and not forcing and int(physics or 0) != 2:
+        raise ValueError("--microphysics kessler needs the MPAS dynamics (--physics 2)")
     physics = 2 if forcing else int(physics) if physics else (1 if transport else 0)
+    rain = None
+    if microphysics:
+        transport = 2
+        jw.add_moisture(st, m)
+        st["rt_diabatic_tend"][...] = 0.0
+        water0 = moist.total_water(st)
+        log("microphysics kessler: the dynamics do not feel water loading yet (qtot, cqw, cqu stay constants): "
+            "a smoke run, not a validation of the DCMIP-2016 case")
     if stats and physics != 2:
         raise ValueError("--stats needs the MPAS dynamics (--physics 2 or --forcing held-suarez)")
     sigma = list(sigma_levels) if sigma_levels is not None else list(DEFAULT_SIGMA)
@@ -69,6 +92,8 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         ctx.set_option("transport", int(transport))
         if forcing:
             ctx.set_option("forcing", 1)
+        if microphysics:
+            ctx.set_option("microphysics", 1)
         ctx.upload(st)
         if physics == 2:  # MPAS-A's atm_core_init diagnostics of the initial state
             T.atm_compute_solve_diagnostics(ctx, False, -1)
@@ -89,6 +114,8 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         if stats:
             acc = T.sigma_stats_read(ctx)
             samples = ctx.get_option("stats_samples")
+        if microphysics:
+            rain = T.precip_read(ctx)["rain"]
         ctx.download(st)
     if physics == 2:
         sp = st["surface_pressure"][:nC, 0] / 100.0
@@ -101,6 +128,12 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         uz = np.abs(st["uReconstructZonal"][:nC, :L])
         log(f"{forcing}: lowest-level temperature mean {float(np.sum(t0 * area) / np.sum(area)):.4f} K; "
             f"max |uReconstructZonal| {float(uz.max()):.4f} m/s")
+    if microphysics:
+        lo, hi, mean = moist.precip_summary(st, rain)
+        q = st["scalars"][:nC, :L, :3]
+        log(f"kessler: accumulated precipitation min {lo:.6g} max {hi:.6g} area mean {mean:.6g} mm; "
+            f"water budget change {moist.total_water(st, rain) / water0 - 1.0:.3e}; smallest qv, qc, qr "
+            f"{q[..., 0].min():.3g}, {q[..., 1].min():.3g}, {q[..., 2].min():.3g}")
     if stats:
         z = zonal_means(acc, st["lat"][:nC, 0], 1.0 / st["invAreaCell"][:nC, 0], stats_bands)
         np.savez(stats, sigma=np.array(sigma), samples=samples, **z)
@@ -114,7 +147,7 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
             log(f"stats: {samples} samples, no sigma level sampled -> {stats}")
     if out:
         from .meshio import write_output_plotting
-        write_output_plotting(out, m, st)
+        write_output_plotting(out, m, st, extra={"rain": rain} if microphysics else None)
     return st
 
 
@@ -141,6 +174,9 @@ def main(argv=None):
     ap.add_argument("--stats-after-days", type=float, default=0.0, help="spin-up: the accumulators are zeroed after D days")
     ap.add_argument("--sigma-levels", default=None, help="comma-separated, in (0, 1], decreasing (default 0.975, ..., 0.025)")
     ap.add_argument("--stats-bands", type=int, default=36, help="latitude bands of the zonal means")
+    ap.add_argument("--microphysics", choices=["kessler"], default=None,
+                    help="kessler: the moist JW state and the warm-rain task at the end of every step (needs --physics 2; "
+                         "implies --transport --transport-scheme rk3)")
     a = ap.parse_args(argv)
     from . import mesh as M
     if a.grid:
@@ -155,7 +191,7 @@ def main(argv=None):
     sigma = [float(x) for x in a.sigma_levels.split(",")] if a.sigma_levels else None
     run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out, forcing=a.forcing,
         stats=a.stats, stats_every=a.stats_every, stats_after_days=a.stats_after_days, sigma_levels=sigma,
-        stats_bands=a.stats_bands)
+        stats_bands=a.stats_bands, microphysics=a.microphysics)
     return 0
 
 

@@ -237,6 +237,27 @@ def init_atm_case_jw(m, st, perturb=False):
     return st
 
 
+Q0, LATW, PW = 0.018, 2.0 * np.pi / 9.0, 34000.0
+
+
+def add_moisture(st, m):
+    """The analytic humidity of the DCMIP-2016 moist baroclinic wave on the JW state st (mesh m): specific
+    humidity q = q0 exp(-(lat/latw)^4) exp(-((eta - 1) p0 / pw)^2) with eta = p / ps of the JW state, 1e-12
+    above eta = 0.1; scalars 0, 1, 2 = qv = q / (1 - q), qc = 0, qr = 0.  theta_m and rho_zz stay the JW
+    state's: the test case reads the JW temperature as the virtual one, so the state is as balanced as the
+    dry one (the dynamics do not yet feel water loading).  Returns st."""
+    nC, L = m.nCells, st.L
+    p = st["pressure_base"][:nC, :L] + st["pressure_p"][:nC, :L]
+    eta = p / st["surface_pressure"][:nC, 0][:, None]
+    lat = np.asarray(m.latCell, dtype=np.float64)[:, None]
+    q = Q0 * np.exp(-(lat / LATW) ** 4) * np.exp(-((eta - 1.0) * P0 / PW) ** 2)
+    q = np.where(eta > 0.1, q, 1.0e-12)
+    st["scalars"][:nC, :L, 0] = q / (1.0 - q)
+    st["scalars"][:nC, :L, 1] = 0.0
+    st["scalars"][:nC, :L, 2] = 0.0
+    return st
+
+
 # the 3-D fields init_atm_case_jw writes (the rest of the state stays 0)
 JW_FIELDS = ("zgrid", "zz", "zxu", "dss", "pressure_base", "rho_base", "rtheta_base", "exner_base", "exner",
              "pressure_p", "rho_p", "rho_zz", "theta_m", "rtheta_p", "surface_pressure", "u", "ru", "v", "rw", "w",

@@ -208,12 +208,13 @@ OUTPUT_STATE_VARS = {"u": "nEdges", "v": "nEdges", "w": "nCells", "pressure": "n
                      "rho": "nCells", "theta": "nCells", "surface_pressure": "nCells"}
 
 
-def write_output_plotting(path, m, st):
+def write_output_plotting(path, m, st, extra=None):
     """timestep_output.nc as mesh_loading.rg:810-1191 writes it: the grid variables,
     indexToCellID/EdgeID/VertexID (1-based), and level 0 of u, v (edges), w, pressure,
     pressure_p, rho, theta, surface_pressure (cells) from the state st (e.g. after
     atm_compute_output_diagnostics and a download).  Grid variables the Mesh does not
-    hold (dv1Edge, dv2Edge for the generated meshes) are left out."""
+    hold (dv1Edge, dv2Edge for the generated meshes) are left out.  extra: per-cell arrays written beside
+    them under their names (the driver's accumulated rain)."""
     from scipy.io import netcdf_file
     dims = {"nCells": m.nCells, "nEdges": m.nEdges, "nVertices": m.nVertices,
             "maxEdges": m.edgesOnCell.shape[1], "maxEdges2": m.edgesOnEdge.shape[1], "TWO": 2,
@@ -235,6 +236,8 @@ def write_output_plotting(path, m, st):
         for v, dim in OUTPUT_STATE_VARS.items():
             n = dims[dim]
             f.createVariable(v, "f8", (dim,))[:] = np.asarray(st[v])[:n, 0]
+        for v, a in (extra or {}).items():
+            f.createVariable(v, "f8", ("nCells",))[:] = np.asarray(a, dtype=np.float64)[:m.nCells]
 
 
 def main(argv=None):

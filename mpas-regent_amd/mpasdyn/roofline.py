@@ -266,6 +266,12 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
         # (stats_acc_bytes) -- they are state, read and written once per sample, not scratch
         return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "uReconstructZonal",
                  "uReconstructMeridional", "rdzw"], [])
+    if task == "atm_kessler_microphysics":  # k_kessler.hip (option microphysics; no reference task)
+        # seven C3 columns read, five written; of scalars the two pair columns that hold qv, qc, qr (and scalar 3,
+        # stored back as found), read and written: b_alg counts them (kessler_extra_bytes) in place of the whole
+        # x8 field, with the three per-cell accumulators -- state, read and written once per call, not scratch
+        return (["theta_m", "rtheta_p", "rho_zz", "zz", "exner", "rtheta_base", "exner_base", "rdzw"],
+                ["theta_m", "rtheta_p", "exner", "pressure_p", "rt_diabatic_tend"])
     if task in ("stepkeep_restore_w", "stepkeep_save_w"):  # option stepkeep = 2 (no reference task)
         # one cell column read, one written: w from (to) the scratch copy of the w stage 0's dyn_tend leaves
         return ["w"], ["w"]
@@ -305,12 +311,20 @@ def stats_acc_bytes(nCells, nsigma):
     return 8 * nCells * (9 * nsigma + 3)
 
 
+def kessler_extra_bytes(nCells, L):
+    """the Kessler task's traffic outside whole registry fields: two of the four scalar pair columns read and
+    written, and the accumulators (rain, the last call's, calls) read and written, fp64"""
+    return 2 * (8 * nCells * L * 4) + 2 * (8 * nCells * 3)
+
+
 def b_alg(task, dims, nsigma=20, **kw):
     """algorithmic bytes of one launch of `task` at dims = (nCells, nEdges, nVertices, L)
     (nsigma: the configured targets of atm_sigma_stats_accumulate, whose accumulators are read and written)"""
     reads, writes = _sets(task, **kw)
     if task == "atm_sigma_stats_accumulate":
         return sum(field_bytes(x, *dims) for x in reads) + 2 * stats_acc_bytes(dims[0], nsigma)
+    if task == "atm_kessler_microphysics":
+        return sum(field_bytes(x, *dims) for x in reads + writes) + kessler_extra_bytes(dims[0], dims[3])
 
     def fb(x):
         b = field_bytes(x, *dims)

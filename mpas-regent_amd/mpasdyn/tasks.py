@@ -193,6 +193,34 @@ def sigma_stats_read(ctx, n_owned=None):
     return out
 
 
+# ---- Kessler warm-rain microphysics (k_kessler.hip; include/mpas_dyn.h, restated by tests/kessler_ref.py)
+PRECIP = ("rain", "rain_last", "calls")  # mpas_precip_read's accumulator 0..2
+
+
+def atm_kessler_microphysics(ctx, dt):
+    """the Kessler task over dt on the state as found: theta_m, rtheta_p, exner, pressure_p, rt_diabatic_tend
+    and scalars 0..2 (qv, qc, qr) of every owned cell; the surface rain goes to the accumulators"""
+    ctx._check(ctx.lib.mpas_atm_kessler_microphysics(ctx.h, float(dt)), "atm_kessler_microphysics")
+
+
+def precip_read(ctx, n_owned=None):
+    """the precipitation accumulators of the owned cells (the first n_owned local cells; default: all): a
+    dict of [n_owned] arrays "rain" (accumulated, mm), "rain_last" (the last call's, mm) and
+    "calls" (the number of calls)"""
+    import numpy as np
+    n = ctx.dims[0] if n_owned is None else int(n_owned)
+    out = {}
+    for i, name in enumerate(PRECIP):
+        a = np.zeros(ctx.dims[0])  # (the call writes every owned cell)
+        ctx._check(ctx.lib.mpas_precip_read(ctx.h, i, a.ctypes.data, a.strides[0]), f"precip_read {name}")
+        out[name] = a[:n].copy()
+    return out
+
+
+def precip_reset(ctx):
+    ctx._check(ctx.lib.mpas_precip_reset(ctx.h), "precip_reset")
+
+
 def summarize_timestep(ctx, config_print_detailed_minmax_vel=False, config_print_global_minmax_vel=False,
                        config_print_global_minmax_sca=False):
     """rk_timestep.rg:29; returns the 31 values the reference prints (layout: include/mpas_dyn.h)"""

@@ -3,7 +3,7 @@
 K atm_srk3 steps (HIP graph replay, as bench.py times them) under each option set (options a variant does not name at their defaults); per
 variant the median per-step device time over all rounds (HIP events between steps).
 
-usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport] [--sigma-levels N]
+usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport] [--sigma-levels N] [--microphysics]
        --variants "fusesetup=1" "fusesetup=0"
 """
 import argparse
@@ -31,15 +31,24 @@ def main():
     ap.add_argument("--transport", action="store_true", help="physics 1 + the scalar transport (bench --transport)")
     ap.add_argument("--sigma-levels", type=int, default=0,
                     help="configure N sigma targets of the sigma-level statistics (physics 2): stats_every usable")
+    ap.add_argument("--microphysics", action="store_true",
+                    help="physics 2 with the RK3 transport on the driver's moist JW state (not the synthetic fill), qc = qr "
+                         "= 2e-3 below 5 km: a variant may set microphysics=1")
     a = ap.parse_args()
-    physics = max(a.physics, 1 if a.transport else 0)
+    physics = 2 if a.microphysics else max(a.physics, 1 if a.transport else 0)
     m, st = bench.build_inputs(a.ncells, a.levels, zero_based=physics)
     ctx = lib.Context(m.nCells, m.nEdges, m.nVertices, a.levels)
     ctx.set_option("physics", physics)
-    ctx.set_option("transport", int(a.transport))
+    ctx.set_option("transport", 2 if a.microphysics else int(a.transport))
     if a.sigma_levels:  # N targets evenly spaced in (0, 1): 0.975, 0.925, ... at N = 20
         T.sigma_stats_configure(ctx, [1.0 - (j + 0.5) / a.sigma_levels for j in range(a.sigma_levels)])
-    bench.upload_inputs(ctx, st)
+    if a.microphysics:  # (the synthetic fill is no atmosphere the scheme is defined on)
+        from mpasdyn import moist
+        ctx.upload(moist.add_rain(moist.moist_jw_state(m, a.levels), 2e-3, 2e-3, 5000.0))
+        T.atm_compute_solve_diagnostics(ctx, False, -1)
+        T.mpas_reconstruct_2d(ctx, False, True)
+    else:
+        bench.upload_inputs(ctx, st)
     dt = bench.dt_for(a.ncells)
     hip = bench.Hip()
     stream = ctx.stream()
@@ -67,7 +76,8 @@ def main():
             res[v] += [hip.elapsed_ms(evs[i], evs[i + 1]) for i in range(a.steps)]
     out = {v: {"median_ms": round(statistics.median(x), 4), "min_ms": round(min(x), 4), "n": len(x)}
            for v, x in res.items()}
-    out["workload"] = f"x1.{a.ncells} x {a.levels}, physics {physics}, transport {int(a.transport)}"
+    out["workload"] = f"x1.{a.ncells} x {a.levels}, physics {physics}, transport {ctx.get_option('transport')}" + \
+        (", moist JW state with rain" if a.microphysics else "")
     print(json.dumps(out), flush=True)
 
 

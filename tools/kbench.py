@@ -4,10 +4,16 @@ workload once and runs interleaved rounds of full RK3 steps under each option se
 reporting the median per-task device time (HIP events on the task stream).
 
 usage: python tools/kbench.py [--ncells 163842] [--levels 56] [--rounds 5] [--physics N] [--transport]
-       [--sigma-levels N] --variants "xcd=1" "xcd=0"
+       [--sigma-levels N] [--microphysics] --variants "xcd=1" "xcd=0"
 
 --sigma-levels N (physics 2) configures N sigma targets of the sigma-level statistics first (the driver's
 default list at 20), so that a variant may set stats_every=1 and the task's row appears.
+
+--microphysics times the Kessler warm-rain task (physics 2) per direct launch instead of the step's rows, on two
+states in interleaved rounds: "jw", the driver's moist JW state as initialised (n = 1 everywhere, the floor), and
+"rain", the same with qc = qr = 2e-3 below 5 km.  What the task writes is uploaded again before every timed call,
+so every round sees the same state.  Per state: the median time, the distribution of the subcycle count n, the
+algorithmic bytes and TB/s, and the time per subcycle of the slowest wavefront (ms / max n).
 """
 import argparse
 import json
@@ -15,12 +21,53 @@ import os
 import statistics
 import sys
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "mpas-regent_amd")]
 
 import bench  # noqa: E402
 from mpasdyn import lib  # noqa: E402
 from mpasdyn import tasks as T  # noqa: E402
+
+
+def microphysics(a):
+    from mpasdyn import mesh, moist, roofline
+    m = mesh.zero_based(mesh.icosahedral(bench.LEVEL_OF[a.ncells]))
+    st = moist.moist_jw_state(m, a.levels)
+    dt = bench.dt_for(a.ncells)
+    nC, L = m.nCells, a.levels
+    dry_scalars = st["scalars"].copy()
+    wet_scalars = moist.add_rain(st, 2e-3, 2e-3, 5000.0)["scalars"].copy()
+    out = {}
+    with lib.Context(m.nCells, m.nEdges, m.nVertices, L) as ctx:
+        ctx.set_option("physics", 2)
+        ctx.upload(st)
+        res = {"jw": [], "rain": []}
+        for r in range(a.rounds + 1):  # (round 0 untimed: first launches)
+            for name, sc in (("jw", dry_scalars), ("rain", wet_scalars)):
+                st["scalars"][...] = sc
+                ctx.upload(st, names=list(moist.KESSLER_FIELDS))
+                ctx.sync()
+                ctx.timing(True)
+                ctx.timing_reset()
+                T.atm_kessler_microphysics(ctx, dt)
+                ctx.sync()
+                if r:
+                    res[name].append(ctx.timing_report()["atm_kessler_microphysics"][1])
+                ctx.timing(False)
+        b = roofline.b_alg("atm_kessler_microphysics", (m.nCells, m.nEdges, m.nVertices, L))
+        for name, sc in (("jw", dry_scalars), ("rain", wet_scalars)):
+            st["scalars"][...] = sc
+            n = moist.subcycles(st, dt)
+            ms = statistics.median(res[name])
+            out[name] = {"ms": round(ms, 4), "min_ms": round(min(res[name]), 4), "rounds": len(res[name]),
+                         "b_alg": b, "TBps": round(b / (ms * 1e-3) / 1e12, 3),
+                         "n": {"min": int(n.min()), "median": float(np.median(n)), "mean": round(float(n.mean()), 3),
+                               "max": int(n.max()), "columns_n1": int((n == 1).sum())},
+                         "ms_per_subcycle_of_max_n": round(ms / int(n.max()), 5)}
+    out["workload"] = f"x1.{a.ncells} x {L}, dt {dt:g}"
+    print(json.dumps(out, indent=1))
 
 
 def main():
@@ -32,7 +79,11 @@ def main():
     ap.add_argument("--physics", type=int, default=0)
     ap.add_argument("--transport", action="store_true", help="physics 1 + the scalar transport (bench --transport)")
     ap.add_argument("--sigma-levels", type=int, default=0, help="configure N sigma targets (physics 2): stats_every usable")
+    ap.add_argument("--microphysics", action="store_true",
+                    help="time the Kessler task per launch on the moist JW state and its rainy variant (see above)")
     a = ap.parse_args()
+    if a.microphysics:
+        return microphysics(a)
     physics = max(a.physics, 1 if a.transport else 0)
     m, st = bench.build_inputs(a.ncells, a.levels, zero_based=physics)
     ctx = lib.Context(m.nCells, m.nEdges, m.nVertices, a.levels)
