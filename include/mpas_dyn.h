@@ -457,6 +457,71 @@ int mpas_atm_sigma_stats_accumulate(mpas_ctx* ctx);
 int mpas_atm_kessler_microphysics(mpas_ctx* ctx, double dt);
 int mpas_precip_read(mpas_ctx* ctx, int32_t which, double* out, int64_t stride_cell);
 int mpas_precip_reset(mpas_ctx* ctx);
+/* Surface fluxes and boundary layer (k_pbl.hip): the bulk surface fluxes of momentum, heat and moisture over an
+ *       ocean of prescribed temperature and the implicit boundary-layer diffusion of the simple-physics package
+ *       of Reed & Jablonowski (2012), the lower boundary the DCMIP-2016 moist cases pair with Kessler.  It is that
+ *       scheme on the model's own layers and layer mass instead of pressure thicknesses, and the mixing ratio qv
+ *       stands where the source has specific humidity; the package's large-scale condensation is left out
+ *       (Kessler's saturation adjustment covers it).  No reference entry point ("physics" = 2, dt > 0 and a
+ *       configured surface temperature, else MPAS_EINVAL).  Per owned cell column, levels k = 0..L-1
+ *       (L = nVertLevels, 0 the lowest), every input as found:
+ *         m = rho_zz / rdzw (Kessler's layer mass);   dz = 1 / (rdzw zz);   rho_d = zz rho_zz
+ *         p = pressure_base + pressure_p;   pi = exner, held fixed over the call;   rvord = 461.6 / 287
+ *         qv = scalar 0;   theta = theta_m / (1 + rvord qv);   ua = uReconstructZonal;   va = uReconstructMeridional
+ *         ps: mpas_atm_held_suarez_forcing's surface-pressure expression, term for term;   Ts: the cell's
+ *         configured surface temperature;   za = 0.5 dz(0);   wind = sqrt(ua(0)^2 + va(0)^2)
+ *         Cd = wind < 20 ? 7e-4 + 6.5e-5 wind : 2e-3;   Ch = 1.1e-3
+ *         qss = 0.622 / ps * 610.78 * exp(-(2.5e6 / 461.5) (1 / Ts - 1 / 273.16))
+ *         am = Cd wind dt / za;   ah = Ch wind dt / za
+ *       The surface step, implicit, level 0 only (the other levels carry over):
+ *         u1(0) = ua(0) / (1 + am);   v1(0) = va(0) / (1 + am)
+ *         th1(0) = (theta(0) + ah Ts / pi(0)) / (1 + ah);   q1(0) = (qv(0) + ah qss) / (1 + ah)
+ *         E = m(0) (q1(0) - qv(0))   (kg/m2 = mm: the evaporation of the call)
+ *       The mixing at the interfaces k = 1..L-1, between levels k-1 and k, with D(0) = D(L) = 0:
+ *         s = dz(k) + dz(k-1);   pint = (dz(k) p(k-1) + dz(k-1) p(k)) / s;   rhoi likewise from rho_d;   dzc = 0.5 s
+ *         f = pint >= 85000 ? 1 : exp(-((85000 - pint) / 10000)^2)
+ *         Dm(k) = rhoi Cd wind za f / dzc;   Dh(k) = the same with Ch
+ *       then one implicit flux-form step per quantity, with Dm for u1 and v1 and Dh for th1 and q1:
+ *         a(k) = -dt D(k) / m(k);   c(k) = -dt D(k+1) / m(k);   b = 1 - a - c
+ *         a(k) X2(k-1) + b(k) X2(k) + c(k) X2(k+1) = X1(k)
+ *       solved by the Thomas algorithm level by level in the order tests/pbl_ref.py states (one reciprocal per
+ *       level, shared by the two right-hand sides of a system); each step conserves sum_k m X.  Cd and f are
+ *       continuous at their switches.  Written, by Kessler's increment forms from th2 and q2:
+ *         theta_m' = theta_m + (th2 - theta)(1 + rvord q2) + theta rvord (q2 - qv)
+ *         rtheta_p' = rtheta_p + rho_zz (theta_m' - theta_m)
+ *         exner, pressure_p from rtheta_p' by atm_recover_large_step_variables_work's two expressions (MPAS form)
+ *         scalar 0 = q2 (scalar 1, which shares its 16-byte pair, is stored back as found)
+ *       and, per owned edge with cells c1, c2 and A = angleEdge, the momentum change as a tendency:
+ *         Fu = rho_zz (u2 - ua) / dt;   Fv = rho_zz (v2 - va) / dt   (per cell, scratch)
+ *         tend_ru_physics = 0.5 (Fu(c1) + Fu(c2)) cos A + 0.5 (Fv(c1) + Fv(c2)) sin A
+ *       and no other field: rt_diabatic_tend, uReconstructZonal / Meridional and u are not written, scalars 1..7,
+ *       level nVertLevels and the zero slot keep their bits.  Momentum goes through tend_ru_physics, as MPAS-A
+ *       projects its boundary-layer wind tendencies onto the edges (a direct write of u would leave
+ *       solve_diagnostics' ke, pv_edge and v stale); heat and moisture are time-split state updates like Kessler's,
+ *       because the transport has no scalar tendency slot.  A column with wind = 0 keeps theta_m, rtheta_p and qv
+ *       bit for bit (exner and pressure_p where they satisfy the two expressions as found) and gets
+ *       Fu = Fv = +0.0 and E = +0.0; L = 1 is the surface step alone.  exp, sqrt and the exner expression's pow
+ *       are the only libm calls.  Statement order: tests/pbl_ref.py.  A decomposed context runs its owned cells
+ *       and edges; the edge part gathers Fu, Fv of the ghost cells by an exchange of the scratch.
+ *       Per owned cell three accumulators, plain `+=` in call order, one writer each (two runs give the same
+ *       bits): 0 the accumulated evaporation E (mm), 1 the last call's E, 2 the number of calls (as a double).
+ *       They are not registry fields (mpas_field_count is unchanged) and are allocated, zeroed, on first use.
+ * mpas_surface_set_temperature: Ts of the owned cells in kelvin, cell e at byte offset e*stride_cell; a value that
+ *       is not finite or not > 0 returns MPAS_EINVAL and leaves the configured temperatures as they were.
+ * mpas_surface_flux_read copies accumulator `which` (0..2) of the owned cells to out (the call synchronises): cell
+ *       e at byte offset e*stride_cell.  mpas_surface_flux_reset zeroes all three.
+ * Option "pbl" = 1 (needs "physics" = 2 and a configured Ts, else MPAS_EINVAL; a value other than 0 or 1:
+ *       MPAS_EINVAL; default 0; reset to 0 when "physics" leaves 2) makes mpas_atm_srk3 end every step with the
+ *       task over the step's dt: behind mpas_reconstruct_2d, the substep finish and the Kessler task (the DCMIP
+ *       order, microphysics then simple physics), ahead of a "stats_every" sample, inside the captured graph,
+ *       under the timing key "atm_surface_pbl".  The tendency it leaves is the one the next step's three stages
+ *       read; the first step reads what was uploaded.  With 0 the step is launch for launch the step without the
+ *       feature.  "pbl" = 1 together with "forcing" = 1 is MPAS_EINVAL in whichever order they are set: both
+ *       write tend_ru_physics, and Held-Suarez's Rayleigh layer and this boundary layer are alternatives. */
+int mpas_atm_surface_pbl(mpas_ctx* ctx, double dt);
+int mpas_surface_set_temperature(mpas_ctx* ctx, const double* ts, int64_t stride_cell);
+int mpas_surface_flux_read(mpas_ctx* ctx, int32_t which, double* out, int64_t stride_cell);
+int mpas_surface_flux_reset(mpas_ctx* ctx);
 /* rk_timestep.rg:29 summarize_timestep(cr, er, config_print_detailed_minmax_vel,
  *       config_print_global_minmax_vel, config_print_global_minmax_sca): the values the
  *       reference prints, into out[31] (host memory; the call synchronises):

@@ -74,6 +74,9 @@ const FieldInfo kFields[X_COUNT] = {
     {"w1", K_C3, 1, D_M, 0, 0},
     {"w2", K_C3, 1, D_M, 0, 0},
     {"dkf", K_ZV, 1, D_M, 0, 0},
+    {"pblFu", K_C3, 1, D_M, 0, 0},
+    {"pblFv", K_C3, 1, D_M, 0, 0},
+    {"sinAngleEdge", K_E2F, 1, D_M, 0, 0},
 };
 // translation units with kernels, registered at load time (mpas_dev.h, bounds-checked build)
 static std::vector<void* (*)()>& bounds_tus() {
@@ -125,6 +128,15 @@ struct mpas_ctx {
     // is set, or at the first direct call; never inside a capture)
     int microphysics = 0;
     double* precip = nullptr;
+    // option "pbl" (the MPAS dynamics, physics = 2): 1 -- atm_srk3 ends with the surface-flux and boundary-layer
+    // task (k_pbl.hip) over the step's dt, behind the Kessler task, inside the captured graph; 0: the step is launch
+    // for launch the step without it.  sst: the configured surface temperature per local cell
+    // (mpas_surface_set_temperature; nullptr until then); sflux: the task's accumulators -- three runs of nCells
+    // doubles (accumulated evaporation, the last call's, the calls), not registry fields -- allocated and zeroed on
+    // first use (sflux_ensure: never inside a capture)
+    int pbl = 0;
+    double* sst = nullptr;
+    double* sflux = nullptr;
     int self_on = 1;  // option "self": allow the SELF gathers when the mesh permits
     int self_ok = 0;   // k_prepare's verdict on the uploaded mesh
     int overlap = 1;   // option "overlap": halo exchanges beside interior compute
@@ -1123,7 +1135,7 @@ StepForm step_form(const mpas_ctx* c, double dt, int schedule, int gen) {
     // option stepkeep: the step whose launches the kept generation may thin out -- the headline's order
     // (DESIGN.md §4k lists why each condition is there); anywhere else keep_gen stays 0
     f.stepkeep = c->stepkeep && f.keep && c->ntu == 1 && c->defer4 && f.fcopy && c->accoef && !f.hf && !c->tmedge &&
-                 !c->etile && !c->transport && !c->forcing && !c->microphysics && f.rk_of[0] == 0 && f.rk_of[1] != 0 && f.rk_of[2] != 0;
+                 !c->etile && !c->transport && !c->forcing && !c->microphysics && !c->pbl && f.rk_of[0] == 0 && f.rk_of[1] != 0 && f.rk_of[2] != 0;
     // option vikeep: stage 0's coefficient set in scratch (every generation of a step stepkeep is active for)
     f.vik = c->vikeep && f.stepkeep;
     // option a0keep: a full step leaves the next step's kdiff in X_kd0; a kept step takes it from there and runs
@@ -1472,6 +1484,10 @@ void step_end(mpas_ctx* c, const StepForm& f, StepRun& r) {
     // and the reconstruction; its rt_diabatic_tend is the heating of the next step's dynamics
     if (c->microphysics)
         run_task(c, "atm_kessler_microphysics", [&] { return launch_kessler(S, st, dt, c->precip); });
+    // option pbl: then the surface fluxes and the boundary layer (the DCMIP order: microphysics, then simple
+    // physics); the tend_ru_physics it leaves is the one the next step's three stages read
+    if (c->pbl)
+        run_task(c, "atm_surface_pbl", [&] { return launch_surface_pbl(S, st, dt, c->sst, c->sflux); });
     // :492 summarize_timestep(cr, er, false, false, false) (constants.rg:67-69): prints only
 }
 
@@ -1647,6 +1663,19 @@ void precip_ensure(mpas_ctx* c) {
     hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
 }
 
+// the surface task's accumulators (mpas_ctx::sflux), allocated and zeroed on first use
+void sflux_ensure(mpas_ctx* c) {
+    if (c->sflux) return;
+    const size_t bytes = 3 * (size_t)c->S.nCells * sizeof(double);
+    if (hipMalloc((void**)&c->sflux, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->sflux = nullptr;
+        throw Fail{MPAS_ENOMEM, "hipMalloc surface-flux accumulators"};
+    }
+    hipcheck(hipMemsetAsync(c->sflux, 0, bytes, c->stream), "hipMemsetAsync");
+    hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+}
+
 // one atm_srk3 step, with option stepkeep's bookkeeping: the generation the step runs at, then the one it leaves
 void srk3_step(mpas_ctx* c, double dt, int schedule) {
     const bool act = step_form(c, dt, schedule, 0).stepkeep;
@@ -1753,7 +1782,7 @@ const OptRow kOptions[] = {
     opt("physics", &DevState::physics, O_RANGE, 0, 2, "physics must be 0 (reference), 1 (MPAS vertical solver) or 2 (MPAS dynamics)",
         [](mpas_ctx* c, int64_t& v) {
             if (!v) c->transport = 0;
-            if (v != 2) c->forcing = 0, c->stats_every = 0, c->microphysics = 0;
+            if (v != 2) c->forcing = 0, c->stats_every = 0, c->microphysics = 0, c->pbl = 0;
             c->ett_dirty = true;
         }),
     opt("trorder_e", &DevState::troe, O_RANGE, 0, 1 << 20, "trorder_e must be 0 (trorder's), 1 or a run length >= 2"),
@@ -1783,6 +1812,8 @@ const OptRow kOptions[] = {
         [](mpas_ctx* c, int64_t& v) {
             if (v && c->S.physics != 2)
                 throw Fail{MPAS_EINVAL, "forcing needs physics = 2 (the MPAS forms of dyn_tend consume its tendencies)"};
+            if (v && c->pbl)
+                throw Fail{MPAS_EINVAL, "forcing and pbl both write tend_ru_physics: Rayleigh friction or the boundary layer"};
         }),
     opt("microphysics", &mpas_ctx::microphysics, O_RANGE, 0, 1, "microphysics must be 0 or 1 (Kessler warm rain)",
         [](mpas_ctx* c, int64_t& v) {
@@ -1791,6 +1822,17 @@ const OptRow kOptions[] = {
             if (v) {
                 hipcheck(hipSetDevice(c->device), "hipSetDevice");
                 precip_ensure(c);
+            }
+        }),
+    opt("pbl", &mpas_ctx::pbl, O_RANGE, 0, 1, "pbl must be 0 or 1 (simple-physics surface fluxes and boundary layer)",
+        [](mpas_ctx* c, int64_t& v) {
+            if (v && (c->S.physics != 2 || !c->sst))
+                throw Fail{MPAS_EINVAL, "pbl needs physics = 2 and a surface temperature (mpas_surface_set_temperature)"};
+            if (v && c->forcing)
+                throw Fail{MPAS_EINVAL, "pbl and forcing both write tend_ru_physics: the boundary layer or Rayleigh friction"};
+            if (v) {
+                hipcheck(hipSetDevice(c->device), "hipSetDevice");
+                sflux_ensure(c);
             }
         }),
     opt("stats_every", &mpas_ctx::stats_every, O_RANGE, 0, 0x7fffffff, "stats_every must be >= 0 (steps per sample; 0: none)",
@@ -1976,6 +2018,8 @@ int mpas_ctx_destroy(mpas_ctx* c) {
     if (c->keep_flag) (void)hipFree(c->keep_flag);
     stats_free(c);
     if (c->precip) (void)hipFree(c->precip);
+    if (c->sst) (void)hipFree(c->sst);
+    if (c->sflux) (void)hipFree(c->sflux);
     if (c->sum_out) (void)hipFree(c->sum_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2112,7 +2156,8 @@ int mpas_upload(mpas_ctx* c, int f, const void* host, int64_t se, int64_t sl, in
         if (c->halo) c->halo->stale[f] = 0;  // uploaded ghosts are the global values
         // derived mesh arrays: cos()/sin() on the host with the same libm as the oracle
         struct { int src, dst; double (*fn)(double); } der[] = {
-            {F_angleEdge, X_cosAngleEdge, ::cos}, {F_latEdge, X_cosLatEdge, ::cos}, {F_lat, X_cosLatCell, ::cos},
+            {F_angleEdge, X_cosAngleEdge, ::cos}, {F_angleEdge, X_sinAngleEdge, ::sin},
+            {F_latEdge, X_cosLatEdge, ::cos},     {F_lat, X_cosLatCell, ::cos},
             {F_lat, X_sinLatCell, ::sin},         {F_lon, X_cosLonCell, ::cos},      {F_lon, X_sinLonCell, ::sin}};
         for (const auto& dv : der) {
             if (dv.src != f) continue;
@@ -2538,6 +2583,63 @@ int mpas_precip_reset(mpas_ctx* c) {
         hipcheck(hipSetDevice(c->device), "hipSetDevice");
         precip_ensure(c);
         hipcheck(hipMemsetAsync(c->precip, 0, 3 * (size_t)c->S.nCells * sizeof(double), c->stream), "hipMemsetAsync");
+    }, true);
+}
+// ---- the surface fluxes and the boundary layer (k_pbl.hip): the task, the surface temperature it reads and its
+// accumulators, which are no fields.  A new surface temperature changes what a step with option pbl computes but
+// not its launches: the captured graph reads the same buffer
+int mpas_atm_surface_pbl(mpas_ctx* c, double dt) {
+    return guarded(c, [&] {
+        if (c->S.physics != 2) throw Fail{MPAS_EINVAL, "atm_surface_pbl needs physics = 2 (the MPAS dynamics' state)"};
+        if (!(dt > 0.0)) throw Fail{MPAS_EINVAL, "atm_surface_pbl: dt must be positive"};
+        if (!c->sst) throw Fail{MPAS_EINVAL, "atm_surface_pbl needs a surface temperature (mpas_surface_set_temperature)"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        sflux_ensure(c);
+        run_task(c, "atm_surface_pbl", [&] { return launch_surface_pbl(c->S, c->stream, dt, c->sst, c->sflux); });
+    });
+}
+int mpas_surface_set_temperature(mpas_ctx* c, const double* ts, int64_t stride_cell) {
+    return guarded(c, [&] {
+        if (!ts) throw Fail{MPAS_EINVAL, "mpas_surface_set_temperature: ts must not be null"};
+        const int nCO = c->S.nCO;
+        // (the cells past the owned ones are never read; they hold the last owned value)
+        std::vector<double> h((size_t)c->S.nCells + 1, 0.0);
+        for (int e = 0; e < nCO; e++) {
+            const double v = *(const double*)((const char*)ts + e * stride_cell);
+            if (!std::isfinite(v) || !(v > 0.0))
+                throw Fail{MPAS_EINVAL, "mpas_surface_set_temperature: cell " + std::to_string(e) + " is not a positive finite temperature"};
+            h[(size_t)e] = v;
+        }
+        for (size_t e = (size_t)nCO; e < h.size(); e++) h[e] = nCO ? h[(size_t)nCO - 1] : 300.0;
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        if (!c->sst && hipMalloc((void**)&c->sst, h.size() * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->sst = nullptr;
+            throw Fail{MPAS_ENOMEM, "hipMalloc surface temperature"};
+        }
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        hipcheck(hipMemcpy(c->sst, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }, true);
+}
+int mpas_surface_flux_read(mpas_ctx* c, int which, double* out, int64_t stride_cell) {
+    return guarded(c, [&] {
+        if (which < 0 || which > 2 || !out) throw Fail{MPAS_EINVAL, "mpas_surface_flux_read: which must be 0..2, out not null"};
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        sflux_ensure(c);
+        const int nCO = c->S.nCO;
+        std::vector<double> h((size_t)nCO);
+        if (nCO)
+            hipcheck(hipMemcpyAsync(h.data(), c->sflux + (size_t)which * c->S.nCells, h.size() * sizeof(double),
+                                    hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync D2H");
+        hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        for (int e = 0; e < nCO; e++) *(double*)((char*)out + e * stride_cell) = h[(size_t)e];
+    }, true);
+}
+int mpas_surface_flux_reset(mpas_ctx* c) {
+    return guarded(c, [&] {
+        hipcheck(hipSetDevice(c->device), "hipSetDevice");
+        sflux_ensure(c);
+        hipcheck(hipMemsetAsync(c->sflux, 0, 3 * (size_t)c->S.nCells * sizeof(double), c->stream), "hipMemsetAsync");
     }, true);
 }
 // ---- the sigma-level statistics (k_stats.hip).  None of these calls writes a field or changes the form of the

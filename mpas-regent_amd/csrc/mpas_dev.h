@@ -125,6 +125,11 @@ enum FieldId {
     X_w2,       // stage rewrite w in between)                                                                  C3
     X_dkf,      // one int: 1 when the four columns above hold the running step's values (set by a kept step's
                 // last dyn_tend, cleared by a full step), else 0                                               ZV
+    // surface fluxes and boundary layer (k_pbl.hip); appended here so that no id above moves
+    X_pblFu,    // the momentum tendency of the task per cell and level, rho_zz (u2 - ua) / dt and the same for v
+    X_pblFv,    // (zeros from level L up): formed by the cell kernel, gathered at the two cells of each edge and
+                // projected onto the edge normal by the edge kernel                                            C3
+    X_sinAngleEdge,  // sin(angleEdge), computed at upload beside X_cosAngleEdge (glibc sin on the host)       E2F
     X_COUNT
 };
 
@@ -405,6 +410,16 @@ constexpr double kKsXk = 0.2875;
 constexpr double kKsPsl = 1000.0;    // hPa
 constexpr int kKsMaxSub = 4096;      // most sedimentation subcycles of a call (never reached inside the contract)
 hipError_t launch_kessler(const DevState& S, hipStream_t st, double dt, double* precip);
+// Surface fluxes and boundary layer (k_pbl.hip; the MPAS dynamics; identical to tests/pbl_ref.py): theta_m, rtheta_p,
+// exner, pressure_p and scalar 0 of the owned cells, tend_ru_physics of the owned edges.  sst: the surface
+// temperature per local cell; sflux: three runs of nCells doubles -- accumulated evaporation (mm), the last call's,
+// the number of calls -- not registry fields
+constexpr double kPblCd0 = 7.0e-4, kPblCd1 = 6.5e-5, kPblCdMax = 2.0e-3;  // Cd = Cd0 + Cd1 |v| below ...
+constexpr double kPblWindSw = 20.0;                                      // ... 20 m/s, CdMax from there (continuous)
+constexpr double kPblCh = 1.1e-3;                                        // heat and moisture exchange
+constexpr double kPblPTop = 85000.0, kPblPDecay = 10000.0;               // full mixing below 850 hPa, 100 hPa decay above
+constexpr double kPblEps = 0.622, kPblE0 = 610.78, kPblLvRv = 2.5e6 / 461.5, kPblT00 = 273.16;  // qss of the surface
+hipError_t launch_surface_pbl(const DevState& S, hipStream_t st, double dt, const double* sst, double* sflux);
 hipError_t launch_damping_coefs(const DevState& S, hipStream_t st, double zd, double xnutr);
 hipError_t launch_compute_signs(const DevState& S, hipStream_t st);
 // strided device view <-> LP-padded 3-D field (elem 8: fp64, 1: uint8 masks)

@@ -8,7 +8,7 @@ state -> atm_core_init's one-time precompute -> time steps -> atm_compute_output
                              [--forcing held-suarez] [--days N]
                              [--stats OUT.npz] [--stats-every N] [--stats-after-days D]
                              [--sigma-levels S0,S1,...] [--stats-bands B]
-                             [--microphysics kessler]
+                             [--microphysics kessler] [--pbl simple] [--sst tj16|KELVIN]
 
 Without --grid the reference's own x1.2562 mesh (tests/golden fixture) is used.  The mesh
 is taken in mpas-mode (0-based) ids, the ids the JW state (mpasdyn/jw.py) is defined on.
@@ -39,7 +39,13 @@ rt_diabatic_tend starts at 0, and every step ends with the Kessler warm-rain tas
 include/mpas_dyn.h).  The final report gives the accumulated precipitation (min / max / area mean, mm) and the
 water budget sum(area m (qv + qc + qr)) + sum(area rain) relative to its initial value; the accumulated rain goes
 into the output file as `rain`.  The dynamics do not yet feel water loading, and the log says so: a smoke run,
-not a validation of the DCMIP case."""
+not a validation of the DCMIP case.  `--pbl simple` (needs `--physics 2`, excludes `--forcing`; the moist JW state and
+the RK3 transport with it, as `--microphysics`) ends every step with the surface-flux and boundary-layer task
+(option "pbl" = 1, include/mpas_dyn.h: the simple physics of Reed & Jablonowski 2012 without its large-scale
+condensation) over the sea-surface temperature `--sst`: `tj16` (default), 271 + 29 exp(-lat^2 / (2 (26 deg)^2)) of
+Thatcher & Jablonowski (2016), or one temperature in kelvin.  The final report then gives the accumulated evaporation
+beside the rain and the budget sum(area m (qv + qc + qr)) + sum(area (rain - evaporation)) relative to the initial
+water; the accumulated evaporation goes into the output file as `evaporation`."""
 import argparse
 import os
 import sys
@@ -49,13 +55,15 @@ import numpy as np
 
 def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=False, out=None, device=0,
         log=print, forcing=None, stats=None, stats_every=1, stats_after_days=0.0, sigma_levels=None, stats_bands=36,
-        microphysics=None):
+        microphysics=None, pbl=None, sst="tj16"):
     """transport: False / 0 none, True / 1 one monotonic update per step, 2 the RK3 transport;
     forcing: None or "held-suarez" (the MPAS dynamics: physics becomes 2);
     stats: None or the .npz path the zonal-mean sigma-level statistics are written to (physics 2);
-    microphysics: None or "kessler" (needs physics 2; the RK3 transport and the moist JW state with it)"""
+    microphysics: None or "kessler" (needs physics 2; the RK3 transport and the moist JW state with it);
+    pbl: None or "simple" (needs physics 2, no forcing; the same state and transport) over the surface temperature
+    sst: "tj16" or kelvin"""
     from . import build_state as bs
-    from . import jw, lib, moist
+    from . import jw, lib, moist, surface
     from . import mesh as M
     from . import tasks as T
     from .stats import DEFAULT_SIGMA, zonal_means
@@ -63,21 +71,26 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         m = M.zero_based(m)
     st = bs.build_state(m, L, "physical", vertical=False)
     # (the moist run is the baroclinic wave: with the test case's zonal-wind perturbation, which the dry runs leave out)
-    jw.init_atm_case_jw(m, st, perturb=bool(microphysics))
+    jw.init_atm_case_jw(m, st, perturb=bool(microphysics or pbl))
     if forcing not in (None, "held-suarez"):
         raise ValueError(f"unknown forcing {forcing!r}")
     if microphysics not in (None, "kessler"):
         raise ValueError(f"unknown microphysics {microphysics!r}")
     if microphysics and not forcing and int(physics or 0) != 2:
         raise ValueError("--microphysics kessler needs the MPAS dynamics (--physics 2)")
+    if pbl not in (None, "simple"):
+        raise ValueError(f"unknown pbl {pbl!r}")
+    if pbl and (forcing or int(physics or 0) != 2):
+        raise ValueError("--pbl simple needs the MPAS dynamics (--physics 2) and excludes --forcing (both write "
+                         "tend_ru_physics: Rayleigh friction or the boundary layer)")
     physics = 2 if forcing else int(physics) if physics else (1 if transport else 0)
-    rain = None
-    if microphysics:
+    rain = evap = None
+    if microphysics or pbl:
         transport = 2
         jw.add_moisture(st, m)
         st["rt_diabatic_tend"][...] = 0.0
         water0 = moist.total_water(st)
-        log("microphysics kessler: the dynamics do not feel water loading yet (qtot, cqw, cqu stay constants): "
+        log(f"{'microphysics kessler' if microphysics else 'pbl simple'}: the dynamics do not feel water loading yet (qtot, cqw, cqu stay constants): "
             "a smoke run, not a validation of the DCMIP-2016 case")
     if stats and physics != 2:
         raise ValueError("--stats needs the MPAS dynamics (--physics 2 or --forcing held-suarez)")
@@ -94,6 +107,10 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
             ctx.set_option("forcing", 1)
         if microphysics:
             ctx.set_option("microphysics", 1)
+        if pbl:
+            T.surface_set_temperature(ctx, surface.sst_tj16(np.asarray(m.latCell)) if sst == "tj16"
+                                      else surface.sst_constant(float(sst)))
+            ctx.set_option("pbl", 1)
         ctx.upload(st)
         if physics == 2:  # MPAS-A's atm_core_init diagnostics of the initial state
             T.atm_compute_solve_diagnostics(ctx, False, -1)
@@ -116,6 +133,8 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
             samples = ctx.get_option("stats_samples")
         if microphysics:
             rain = T.precip_read(ctx)["rain"]
+        if pbl:
+            evap = T.surface_flux_read(ctx)["evap"]
         ctx.download(st)
     if physics == 2:
         sp = st["surface_pressure"][:nC, 0] / 100.0
@@ -134,6 +153,12 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
         log(f"kessler: accumulated precipitation min {lo:.6g} max {hi:.6g} area mean {mean:.6g} mm; "
             f"water budget change {moist.total_water(st, rain) / water0 - 1.0:.3e}; smallest qv, qc, qr "
             f"{q[..., 0].min():.3g}, {q[..., 1].min():.3g}, {q[..., 2].min():.3g}")
+    if pbl:
+        lo, hi, mean = surface.evap_summary(st, evap)
+        uz = np.abs(st["uReconstructZonal"][:nC, :L])
+        log(f"pbl: accumulated evaporation min {lo:.6g} max {hi:.6g} area mean {mean:.6g} mm; "
+            f"E - P budget change {moist.total_water_budget(st, rain, evap) / water0 - 1.0:.3e}; "
+            f"max |uReconstructZonal| {float(uz.max()):.4f} m/s; smallest qv {st['scalars'][:nC, :L, 0].min():.3g}")
     if stats:
         z = zonal_means(acc, st["lat"][:nC, 0], 1.0 / st["invAreaCell"][:nC, 0], stats_bands)
         np.savez(stats, sigma=np.array(sigma), samples=samples, **z)
@@ -147,7 +172,8 @@ def run(m, L, steps, dt, schedule=1, physics=0, transport=False, dt_from_step=Fa
             log(f"stats: {samples} samples, no sigma level sampled -> {stats}")
     if out:
         from .meshio import write_output_plotting
-        write_output_plotting(out, m, st, extra={"rain": rain} if microphysics else None)
+        extra = dict({"rain": rain} if microphysics else {}, **({"evaporation": evap} if pbl else {}))
+        write_output_plotting(out, m, st, extra=extra or None)
     return st
 
 
@@ -177,6 +203,10 @@ def main(argv=None):
     ap.add_argument("--microphysics", choices=["kessler"], default=None,
                     help="kessler: the moist JW state and the warm-rain task at the end of every step (needs --physics 2; "
                          "implies --transport --transport-scheme rk3)")
+    ap.add_argument("--pbl", choices=["simple"], default=None,
+                    help="simple: bulk surface fluxes and boundary-layer mixing at the end of every step (needs --physics 2, "
+                         "excludes --forcing; the moist JW state and the RK3 transport with it)")
+    ap.add_argument("--sst", default="tj16", help="with --pbl: tj16 (271 + 29 exp(-lat^2 / (2 (26 deg)^2))) or kelvin")
     a = ap.parse_args(argv)
     from . import mesh as M
     if a.grid:
@@ -191,7 +221,7 @@ def main(argv=None):
     sigma = [float(x) for x in a.sigma_levels.split(",")] if a.sigma_levels else None
     run(m, a.levels, steps, a.dt, a.schedule, a.physics, transport, a.dt_from_step, a.out, forcing=a.forcing,
         stats=a.stats, stats_every=a.stats_every, stats_after_days=a.stats_after_days, sigma_levels=sigma,
-        stats_bands=a.stats_bands, microphysics=a.microphysics)
+        stats_bands=a.stats_bands, microphysics=a.microphysics, pbl=a.pbl, sst=a.sst)
     return 0
 
 

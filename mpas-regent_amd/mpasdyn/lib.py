@@ -28,6 +28,7 @@ EXPORTS = [
     "mpas_atm_advance_scalars", "mpas_atm_advance_scalars_mono_rk", "mpas_atm_held_suarez_forcing",
     "mpas_sigma_stats_configure", "mpas_sigma_stats_reset", "mpas_sigma_stats_read", "mpas_atm_sigma_stats_accumulate",
     "mpas_atm_kessler_microphysics", "mpas_precip_read", "mpas_precip_reset",
+    "mpas_atm_surface_pbl", "mpas_surface_set_temperature", "mpas_surface_flux_read", "mpas_surface_flux_reset",
     "mpas_atm_compute_damping_coefs", "mpas_atm_init_coupled_diagnostics", "mpas_atm_core_init",
     "mpas_halo_ring1", "mpas_atm_compute_signs", "mpas_atm_adv_coef_compression", "mpas_atm_couple_coef_3rd_order",
     "mpas_atm_compute_mesh_scaling",
@@ -101,6 +102,10 @@ def load():
         "mpas_atm_kessler_microphysics": (i32, [vp, dbl]),
         "mpas_precip_read": (i32, [vp, i32, vp, i64]),
         "mpas_precip_reset": (i32, [vp]),
+        "mpas_atm_surface_pbl": (i32, [vp, dbl]),
+        "mpas_surface_set_temperature": (i32, [vp, vp, i64]),
+        "mpas_surface_flux_read": (i32, [vp, i32, vp, i64]),
+        "mpas_surface_flux_reset": (i32, [vp]),
         "mpas_atm_compute_damping_coefs": (i32, [vp, dbl, dbl]),
         "mpas_atm_init_coupled_diagnostics": (i32, [vp]),
         "mpas_atm_core_init": (i32, [vp]),

@@ -21,6 +21,16 @@ def total_water(st, rain=None):
     return w + (float(np.sum(area * np.asarray(rain))) if rain is not None else 0.0)
 
 
+def total_water_budget(st, rain=None, evap=None):
+    """sum(area m (qv + qc + qr)) + sum(area (rain - evap)), kg: the budget with the surface source of the
+    boundary-layer task (mpas_atm_surface_pbl) -- the water in the air, plus what rained out, minus what evaporated
+    from the surface (E - P enters with its sign: a closed run keeps this sum)"""
+    nC = st.nCells
+    area = 1.0 / st["invAreaCell"][:nC, 0]
+    w = total_water(st, rain)
+    return w - (float(np.sum(area * np.asarray(evap))) if evap is not None else 0.0)
+
+
 def precip_summary(st, rain):
     """(min, max, area mean) of the accumulated rain, mm"""
     nC = st.nCells

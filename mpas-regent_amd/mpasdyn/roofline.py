@@ -272,6 +272,15 @@ def _sets(task, rk_step=0, small_step=1, reconstruct_v=False, physics=0, damp=Fa
         # x8 field, with the three per-cell accumulators -- state, read and written once per call, not scratch
         return (["theta_m", "rtheta_p", "rho_zz", "zz", "exner", "rtheta_base", "exner_base", "rdzw"],
                 ["theta_m", "rtheta_p", "exner", "pressure_p", "rt_diabatic_tend"])
+    if task == "atm_surface_pbl":  # k_pbl.hip (option pbl; no reference task)
+        # cell kernel: twelve C3 columns read, four written; of scalars the one pair column that holds qv (and
+        # scalar 1, stored back as found), read and written, the surface temperature and the three per-cell
+        # accumulators: b_alg counts them (pbl_extra_bytes).  Edge kernel: the edge's cells and angle read, one E3
+        # column written.  The Fu / Fv scratch the cell kernel stores and the edge kernel gathers (X_pblFu,
+        # X_pblFv) takes no credit, as every scratch
+        return (["pressure_base", "pressure_p", "rho_zz", "qtot", "theta_m", "exner", "rtheta_p", "zz", "rtheta_base",
+                 "exner_base", "uReconstructZonal", "uReconstructMeridional", "rdzw", "cellsOnEdge", "angleEdge"],
+                ["theta_m", "rtheta_p", "exner", "pressure_p", "tend_ru_physics"])
     if task in ("stepkeep_restore_w", "stepkeep_save_w"):  # option stepkeep = 2 (no reference task)
         # one cell column read, one written: w from (to) the scratch copy of the w stage 0's dyn_tend leaves
         return ["w"], ["w"]
@@ -317,6 +326,13 @@ def kessler_extra_bytes(nCells, L):
     return 2 * (8 * nCells * L * 4) + 2 * (8 * nCells * 3)
 
 
+def pbl_extra_bytes(nCells, L):
+    """the surface task's traffic outside whole registry fields: one of the four scalar pair columns read and
+    written, the surface temperature read, and the accumulators (evaporation, the last call's, calls) read and
+    written, fp64"""
+    return 2 * (8 * nCells * L * 2) + 8 * nCells + 2 * (8 * nCells * 3)
+
+
 def b_alg(task, dims, nsigma=20, **kw):
     """algorithmic bytes of one launch of `task` at dims = (nCells, nEdges, nVertices, L)
     (nsigma: the configured targets of atm_sigma_stats_accumulate, whose accumulators are read and written)"""
@@ -325,6 +341,8 @@ def b_alg(task, dims, nsigma=20, **kw):
         return sum(field_bytes(x, *dims) for x in reads) + 2 * stats_acc_bytes(dims[0], nsigma)
     if task == "atm_kessler_microphysics":
         return sum(field_bytes(x, *dims) for x in reads + writes) + kessler_extra_bytes(dims[0], dims[3])
+    if task == "atm_surface_pbl":
+        return sum(field_bytes(x, *dims) for x in reads + writes) + pbl_extra_bytes(dims[0], dims[3])
 
     def fb(x):
         b = field_bytes(x, *dims)

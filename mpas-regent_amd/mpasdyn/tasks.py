@@ -221,6 +221,45 @@ def precip_reset(ctx):
     ctx._check(ctx.lib.mpas_precip_reset(ctx.h), "precip_reset")
 
 
+# ---- surface fluxes and boundary layer (k_pbl.hip; include/mpas_dyn.h, restated by tests/pbl_ref.py)
+SURFACE_FLUX = ("evap", "evap_last", "calls")  # mpas_surface_flux_read's accumulator 0..2
+
+
+def surface_set_temperature(ctx, ts):
+    """the surface temperature of the owned cells, kelvin: an array of at least the owned cells (the first
+    ctx.dims[0] entries are passed; a decomposed context reads its owned ones), or one number for every cell"""
+    import numpy as np
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(ts, dtype=np.float64), (ctx.dims[0],))
+                             if np.ndim(ts) == 0 else np.asarray(ts, dtype=np.float64)[:ctx.dims[0]])
+    if a.shape[0] < ctx.dims[0]:
+        raise ValueError(f"surface_set_temperature: {a.shape[0]} values for {ctx.dims[0]} cells")
+    ctx._check(ctx.lib.mpas_surface_set_temperature(ctx.h, a.ctypes.data, a.strides[0]), "surface_set_temperature")
+
+
+def atm_surface_pbl(ctx, dt):
+    """the surface-flux and boundary-layer task over dt on the state as found: theta_m, rtheta_p, exner,
+    pressure_p and scalar 0 (qv) of every owned cell, tend_ru_physics of every owned edge; the evaporation goes
+    to the accumulators"""
+    ctx._check(ctx.lib.mpas_atm_surface_pbl(ctx.h, float(dt)), "atm_surface_pbl")
+
+
+def surface_flux_read(ctx, n_owned=None):
+    """the surface-flux accumulators of the owned cells (the first n_owned local cells; default: all): a dict
+    of [n_owned] arrays "evap" (accumulated evaporation, mm), "evap_last" (the last call's, mm) and "calls" (the number of calls)"""
+    import numpy as np
+    n = ctx.dims[0] if n_owned is None else int(n_owned)
+    out = {}
+    for i, name in enumerate(SURFACE_FLUX):
+        a = np.zeros(ctx.dims[0])  # (the call writes every owned cell)
+        ctx._check(ctx.lib.mpas_surface_flux_read(ctx.h, i, a.ctypes.data, a.strides[0]), f"surface_flux_read {name}")
+        out[name] = a[:n].copy()
+    return out
+
+
+def surface_flux_reset(ctx):
+    ctx._check(ctx.lib.mpas_surface_flux_reset(ctx.h), "surface_flux_reset")
+
+
 def summarize_timestep(ctx, config_print_detailed_minmax_vel=False, config_print_global_minmax_vel=False,
                        config_print_global_minmax_sca=False):
     """rk_timestep.rg:29; returns the 31 values the reference prints (layout: include/mpas_dyn.h)"""

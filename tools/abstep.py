@@ -3,7 +3,7 @@
 K atm_srk3 steps (HIP graph replay, as bench.py times them) under each option set (options a variant does not name at their defaults); per
 variant the median per-step device time over all rounds (HIP events between steps).
 
-usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport] [--sigma-levels N] [--microphysics]
+usage: python tools/abstep.py [--ncells 163842] [--rounds 6] [--steps 5] [--physics N] [--transport] [--sigma-levels N] [--microphysics] [--pbl]
        --variants "fusesetup=1" "fusesetup=0"
 """
 import argparse
@@ -34,7 +34,11 @@ def main():
     ap.add_argument("--microphysics", action="store_true",
                     help="physics 2 with the RK3 transport on the driver's moist JW state (not the synthetic fill), qc = qr "
                          "= 2e-3 below 5 km: a variant may set microphysics=1")
+    ap.add_argument("--pbl", action="store_true",
+                    help="with --microphysics (implied): the surface temperature of Thatcher & Jablonowski (2016) is "
+                         "configured, so that a variant may set pbl=1")
     a = ap.parse_args()
+    a.microphysics = a.microphysics or a.pbl
     physics = 2 if a.microphysics else max(a.physics, 1 if a.transport else 0)
     m, st = bench.build_inputs(a.ncells, a.levels, zero_based=physics)
     ctx = lib.Context(m.nCells, m.nEdges, m.nVertices, a.levels)
@@ -47,6 +51,10 @@ def main():
         ctx.upload(moist.add_rain(moist.moist_jw_state(m, a.levels), 2e-3, 2e-3, 5000.0))
         T.atm_compute_solve_diagnostics(ctx, False, -1)
         T.mpas_reconstruct_2d(ctx, False, True)
+        if a.pbl:
+            import numpy as np
+            from mpasdyn import surface
+            T.surface_set_temperature(ctx, surface.sst_tj16(np.asarray(m.latCell)))
     else:
         bench.upload_inputs(ctx, st)
     dt = bench.dt_for(a.ncells)

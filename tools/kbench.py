@@ -4,7 +4,7 @@ workload once and runs interleaved rounds of full RK3 steps under each option se
 reporting the median per-task device time (HIP events on the task stream).
 
 usage: python tools/kbench.py [--ncells 163842] [--levels 56] [--rounds 5] [--physics N] [--transport]
-       [--sigma-levels N] [--microphysics] --variants "xcd=1" "xcd=0"
+       [--sigma-levels N] [--microphysics] [--pbl] --variants "xcd=1" "xcd=0"
 
 --sigma-levels N (physics 2) configures N sigma targets of the sigma-level statistics first (the driver's
 default list at 20), so that a variant may set stats_every=1 and the task's row appears.
@@ -14,6 +14,12 @@ states in interleaved rounds: "jw", the driver's moist JW state as initialised (
 "rain", the same with qc = qr = 2e-3 below 5 km.  What the task writes is uploaded again before every timed call,
 so every round sees the same state.  Per state: the median time, the distribution of the subcycle count n, the
 algorithmic bytes and TB/s, and the time per subcycle of the slowest wavefront (ms / max n).
+
+--pbl times the surface-flux and boundary-layer task (physics 2) per direct launch on the driver's moist JW state
+with MPAS-A's initial diagnostics (the cell-centre winds), over the sea-surface temperature of Thatcher &
+Jablonowski (2016), in rounds interleaved with the Held-Suarez forcing task and the Kessler task on the same state
+(the rows it is reported beside).  What the three tasks write is uploaded again before every timed call.  Per task:
+the median time, the algorithmic bytes and the rate B_alg / time in TB/s.
 """
 import argparse
 import json
@@ -70,6 +76,46 @@ def microphysics(a):
     print(json.dumps(out, indent=1))
 
 
+def pbl(a):
+    from mpasdyn import jw, mesh, moist, roofline, surface
+    m = mesh.zero_based(mesh.icosahedral(bench.LEVEL_OF[a.ncells]))
+    st = jw.jw_state(m, a.levels, perturb=True, subset=True,
+                     extra_names=("scalars", "rt_diabatic_tend", "tend_ru_physics", "tend_rtheta_physics"))
+    jw.add_moisture(st, m)
+    dt = bench.dt_for(a.ncells)
+    L = a.levels
+    written = sorted(set(moist.KESSLER_FIELDS) | {"tend_ru_physics", "tend_rtheta_physics"})
+    calls = {"atm_surface_pbl": lambda c: T.atm_surface_pbl(c, dt),
+             "atm_held_suarez_forcing": T.atm_held_suarez_forcing,
+             "atm_kessler_microphysics": lambda c: T.atm_kessler_microphysics(c, dt)}
+    out = {}
+    with lib.Context(m.nCells, m.nEdges, m.nVertices, L) as ctx:
+        ctx.set_option("physics", 2)
+        T.surface_set_temperature(ctx, surface.sst_tj16(np.asarray(m.latCell)))
+        ctx.upload(st)
+        T.atm_compute_solve_diagnostics(ctx, False, -1)
+        T.mpas_reconstruct_2d(ctx, False, True)
+        res = {k: [] for k in calls}
+        for r in range(a.rounds + 1):  # (round 0 untimed: first launches)
+            for name, fn in calls.items():
+                ctx.upload(st, names=written)
+                ctx.sync()
+                ctx.timing(True)
+                ctx.timing_reset()
+                fn(ctx)
+                ctx.sync()
+                if r:
+                    res[name].append(ctx.timing_report()[name][1])
+                ctx.timing(False)
+        for name in calls:
+            b = roofline.b_alg(name, (m.nCells, m.nEdges, m.nVertices, L))
+            ms = statistics.median(res[name])
+            out[name] = {"ms": round(ms, 4), "min_ms": round(min(res[name]), 4), "rounds": len(res[name]),
+                         "b_alg": b, "TBps": round(b / (ms * 1e-3) / 1e12, 3)}
+    out["workload"] = f"x1.{a.ncells} x {L}, dt {dt:g}, moist JW state"
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ncells", type=int, default=163842)
@@ -81,7 +127,11 @@ def main():
     ap.add_argument("--sigma-levels", type=int, default=0, help="configure N sigma targets (physics 2): stats_every usable")
     ap.add_argument("--microphysics", action="store_true",
                     help="time the Kessler task per launch on the moist JW state and its rainy variant (see above)")
+    ap.add_argument("--pbl", action="store_true",
+                    help="time the surface-flux and boundary-layer task per launch beside the forcing and Kessler tasks (see above)")
     a = ap.parse_args()
+    if a.pbl:
+        return pbl(a)
     if a.microphysics:
         return microphysics(a)
     physics = max(a.physics, 1 if a.transport else 0)
