@@ -310,7 +310,24 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         }
     }
 
+    // MODE 2, a slot past NF (the generic tail): the previous substep's damping on the slot's edge,
+    // stored where this cell owns the edge
+    auto damp_slot = [&](int i, double rpe) {
+        const int e = eoc[i], x1 = cc1[i], x2 = cc2[i];
+        const int sh1 = fi(S, F_isShared)[x1], sh2 = fi(S, F_isShared)[x2];
+        const bool on = kl & (e < S.nEdges) & !(sh1 & sh2);
+        rpe = damp_edge<LP>(rpe, colk(fd(S, X_dvB), x1), colk(fd(S, X_dvB), x2), colk(tm_f, x1) + colk(tm_f, x2),
+                            fd(S, F_specZoneMaskEdge)[e], coefp, on);
+        if ((own >> i) & 1) colk(fw(S, X_rupB), e) = PADW(rpe);
+        return rpe;
+    };
+
     if (spec != 0.0) {  // :1698-1703 (column-uniform branch)
+        // (a specified-zone column returns before the flux loop, whose tail stores the damped ru_p of the
+        // edges owned through slots past NF: stored here, or X_rupB keeps a stale column for them)
+        if constexpr (MODE == 2)
+            for (int i = NF; i < ne; i++)
+                if ((own >> i) & 1) damp_slot(i, colk(ru_p, eoc[i]));
         if (kl) {
             rpp = rpp + dts * tend_rho;
             rtp = rtp + dts * tt;
@@ -337,14 +354,7 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     }
     for (int i = NF; i < ne; i++) {
         double rpe = colk(ru_p, eoc[i]);
-        if constexpr (MODE == 2) {
-            const int e = eoc[i], x1 = cc1[i], x2 = cc2[i];
-            const int sh1 = fi(S, F_isShared)[x1], sh2 = fi(S, F_isShared)[x2];
-            const bool on = kl & (e < S.nEdges) & !(sh1 & sh2);
-            rpe = damp_edge<LP>(rpe, colk(fd(S, X_dvB), x1), colk(fd(S, X_dvB), x2), colk(tm_f, x1) + colk(tm_f, x2),
-                                fd(S, F_specZoneMaskEdge)[e], coefp, on);
-            if ((own >> i) & 1) colk(fw(S, X_rupB), e) = PADW(rpe);
-        }
+        if constexpr (MODE == 2) rpe = damp_slot(i, rpe);
         double flux = sgn[i] * dts * cdv[i] * ldz(kl, rpe) * invA;
         rs = sub_if(kl, rs, flux);
         ts = sub_if(kl, ts, flux * 0.5 * (ldz(kl, colk(tm_f, cc2[i])) + ldz(kl, colk(tm_f, cc1[i]))));

@@ -170,6 +170,14 @@ def icosahedral(level, seed=20211015, order=None):
     V, F = _icosahedron()
     for _ in range(level):
         V, F = _subdivide(V, F)
+    return from_triangulation(V, F, seed, order)
+
+
+def from_triangulation(V, F, seed, order):
+    """The MPAS mesh dual to the triangulation F (rows of three point ids, any orientation)
+    of the unit vectors V: cells at the points, Voronoi vertices at the triangle
+    circumcentres, entities numbered along the curve `order`.  The dual is a Voronoi mesh
+    when F is the Delaunay triangulation of V."""
     # renumber cells along the curve
     corder = np.argsort(_order_key(V, order), kind="stable")
     rank = np.empty_like(corder)
@@ -310,6 +318,95 @@ def icosahedral(level, seed=20211015, order=None):
              latVertex=latVertex, lonVertex=lonVertex, xVertex=P[:, 0].copy(), yVertex=P[:, 1].copy(),
              zVertex=P[:, 2].copy(), areaTriangle=areaTriangle, edgesOnVertex=one(edgesOnVertex),
              cellsOnVertex=one(cellsOnVertex), kiteAreasOnVertex=kite)
+    return m
+
+
+def _oriented_area(V, F):
+    a, b, c = V[F[:, 0]], V[F[:, 1]], V[F[:, 2]]
+    return np.sum(np.cross(b - a, c - a) * a, axis=1)
+
+
+def _lawson_flips(V, F):
+    """Restore the Delaunay property of the counter-clockwise triangulation F of the unit
+    vectors V by Lawson edge flips: edge (a, b) of the triangles (a, b, c), (b, a, d) becomes
+    edge (d, c) of (a, d, c), (d, b, c) when d lies above the plane of (a, b, c), i.e. inside
+    its circumcircle on the sphere (n.d > n.a for the unit normal n of (a, b, c))."""
+    tri = [tuple(int(x) for x in t) for t in F]
+    he = {}
+    for i, (a, b, c) in enumerate(tri):
+        he[(a, b)] = he[(b, c)] = he[(c, a)] = i
+    stack = [k for k in he if k[0] < k[1]]
+    while stack:
+        a, b = stack.pop()
+        if (a, b) not in he or (b, a) not in he:
+            continue
+        t1, t2 = he[(a, b)], he[(b, a)]
+        c = next(x for x in tri[t1] if x != a and x != b)
+        d = next(x for x in tri[t2] if x != a and x != b)
+        n = np.cross(V[b] - V[a], V[c] - V[a])
+        n /= np.linalg.norm(n)
+        if np.dot(n, V[d]) > np.dot(n, V[a]) + 1e-14:  # (the margin ends co-circular ties)
+            for k in ((a, b), (b, c), (c, a), (b, a), (a, d), (d, b)):
+                del he[k]
+            tri[t1], tri[t2] = (a, d, c), (d, b, c)
+            he[(a, d)] = he[(d, c)] = he[(c, a)] = t1
+            he[(d, b)] = he[(b, c)] = he[(c, d)] = t2
+            stack += [(min(k), max(k)) for k in ((a, d), (d, b), (b, c), (c, a))]
+    return np.array(tri, dtype=np.int64)
+
+
+def irregular(level=3, extra=5, jitter=0.2, seed=20211015, order=None):
+    """A Voronoi mesh with 4- to 8-sided cells, for the list lengths that no x1.N mesh has
+    (nEdgesOnCell 4, 7, 8; nEdgesOnEdge up to 14) and entity counts that are no multiple of
+    a block's columns.  The icosahedron is bisected `level` times, `extra` randomly chosen
+    triangles are split at their centroid, and the points are moved by
+    jitter * sqrt(4 pi / N) * N(0, 1) in 8 increments of equal size (independent draws of
+    1/sqrt(8) of that deviation, so their sum has it), each normalised back to the
+    sphere.  An increment is halved for the corners of any triangle it would invert or
+    shrink below 5 % of its oriented area, and after each one Lawson flips restore the
+    Delaunay property, so the circumcentre dual (from_triangulation) is a true Voronoi
+    mesh: cell areas and triangle areas each sum to 4 pi.  kiteAreasOnVertex adds two
+    unsigned triangle areas per kite; where a circumcentre lies outside its triangle they
+    are finite and positive but do not sum to the triangle's area.
+
+    Raises ValueError for a cell with more than 8 edges (build_state's restatement of the
+    reference's advCellsForEdge loop holds 10 entries: 1 + 9 overflow with raw 1-based ids)
+    or an edgesOnEdge list longer than its 20-entry row."""
+    order = order or os.environ.get("MPAS_MESH_ORDER", "hilbert")
+    V, F = _icosahedron()
+    for _ in range(level):
+        V, F = _subdivide(V, F)
+    rng = np.random.default_rng(seed)
+    F = F[:, [0, 2, 1]].copy() if _oriented_area(V, F[:1])[0] < 0 else F.copy()
+    assert (_oriented_area(V, F) > 0).all()
+    pick = rng.choice(F.shape[0], size=extra, replace=False)
+    cen = _normalize(V[F[pick]].sum(axis=1))
+    n0 = V.shape[0]
+    a, b, c = F[pick, 0], F[pick, 1], F[pick, 2]
+    p = n0 + np.arange(extra)
+    F[pick] = np.stack([a, b, p], 1)
+    F = np.concatenate([F, np.stack([b, c, p], 1), np.stack([c, a, p], 1)])
+    V = np.concatenate([V, cen])
+    steps = 8
+    h = np.sqrt(4.0 * np.pi / V.shape[0])
+    for _ in range(steps):
+        d = jitter * h / np.sqrt(steps) * rng.standard_normal(V.shape)
+        o0 = _oriented_area(V, F)
+        for _ in range(30):
+            Vn = _normalize(V + d)
+            bad = _oriented_area(Vn, F) < 0.05 * o0
+            if not bad.any():
+                break
+            d[np.unique(F[bad])] *= 0.5
+        else:
+            raise RuntimeError("irregular: an increment that keeps every triangle was not found")
+        V = Vn
+        F = _lawson_flips(V, F)
+    m = from_triangulation(V, F, seed, order)
+    if m.nEdgesOnCell.max() > 8:
+        raise ValueError(f"irregular: a cell with {m.nEdgesOnCell.max()} edges (at most 8; other seed or jitter)")
+    if m.nEdgesOnEdge.max() > 20:
+        raise ValueError("irregular: nEdgesOnEdge exceeds the 20-entry edgesOnEdge row")
     return m
 
 

@@ -68,12 +68,15 @@ def test_bounds_probe_caught():
 # (L = 2), 64 (L = 63; raw 1-based ids: zero slot, non-SELF gathers) and 64 (L = 56, SELF
 # gathers), both RK3 drivers, the MPAS solver / dynamics, the transport, the mesh tasks and
 # the decomposed path (interior / boundary launches, ring-1 ghosts)
+# -- and, on the mesh with 4- to 8-sided cells (tests/test_gpu_irregular_mesh.py: the kernels' list
+# tail loops), the reference tasks, whole steps, MPAS solver / dynamics and the transport at LP 8 and 64
 SELECTION = ["tests/test_gpu_parity.py", "tests/test_gpu_mpas_dynamics.py", "tests/test_gpu_transport.py",
-             "tests/test_gpu_decomp.py"]
+             "tests/test_gpu_decomp.py", "tests/test_gpu_irregular_mesh.py"]
 KSEL = ("((test_task_exact or test_task) and (random-2 or ref-63 or mpas0-56)) or "
         "(test_srk3 and not level_extremes) or test_mesh_tasks or test_atm_core_init or test_summarize or "
         "test_mpas_srk3 or test_srk3_transport or test_transport_task or test_ring1 or test_overlap_morton_mesh or "
-        "test_ragged_partition or test_task_decomposed_equals_single")
+        "test_ragged_partition or test_task_decomposed_equals_single or "
+        "((test_irr_task or test_irr_srk3 or test_irr_steps5 or test_irr_mpas or test_irr_transport) and (L5 or L63))")
 
 
 def test_parity_suite_under_bounds_checks():

@@ -23,7 +23,14 @@ def _state(x1_2562, ids):
 
 @pytest.mark.parametrize("ids", ["raw", "zero_based"])
 def test_mesh_tasks_match_build_state(x1_2562, ids):
-    m, st = _state(x1_2562, ids)
+    n = check_mesh_tasks_match_build_state(x1_2562, ids)
+    assert n.min() >= 6 and (n == 9).mean() > 0.99
+
+
+def check_mesh_tasks_match_build_state(mesh, ids):
+    """(takes the mesh: tests/test_irregular_mesh.py runs it on 4- to 8-sided cells);
+    returns nAdvCellsForEdge"""
+    m, st = _state(mesh, ids)
     got = st.copy()
     for f in DERIVED + ["meshScalingDel2", "meshScalingDel4"]:
         got[f][...] = 0
@@ -42,8 +49,8 @@ def test_mesh_tasks_match_build_state(x1_2562, ids):
     # the tasks did something: the lists, signs and the 2nd-order weights
     nE = st.nEdges
     n = got["nAdvCellsForEdge"][:nE, 0]
-    assert n.min() >= 6 and (n == 9).mean() > 0.99
     assert np.isclose(got["adv_coefs"][:nE].sum(axis=1), got["dvEdge"][:nE, 0]).all()
+    return n
 
 
 def test_mesh_tasks_quirks(x1_2562):

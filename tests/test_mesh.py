@@ -52,6 +52,24 @@ def test_icosahedral_geometry(level):
             assert 0.8 < np.median(getattr(m, k)) / np.median(getattr(f, k)) < 1.25
 
 
+@pytest.mark.parametrize("key,level,order", [("icosahedral(2)", 2, "hilbert"), ("icosahedral(3)", 3, "hilbert"),
+                                             ("icosahedral(4,morton)", 4, "morton")])
+def test_icosahedral_pinned(key, level, order):
+    """every array of the x1.N generator, bit for bit as before icosahedral() was split into
+    the subdivision and from_triangulation (tests/golden/icosahedral_digests.json)"""
+    import json
+    import os
+
+    from helpers import digest
+    with open(os.path.join(os.path.dirname(__file__), "golden", "icosahedral_digests.json")) as f:
+        want = json.load(f)[key]
+    m = mesh.icosahedral(level, order=order)
+    got = {k: digest(v) for k, v in m.__dict__.items() if hasattr(v, "dtype")}
+    assert set(got) == set(want) and len(want) == 33
+    for k in want:
+        assert got[k]["sha"] == want[k]["sha"], k
+
+
 def test_curve_orders_locality():
     """both numberings keep neighbouring cells close; the cube-face Hilbert curve (the
     default) more often than the 3-D Morton key"""

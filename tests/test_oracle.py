@@ -118,9 +118,14 @@ def np_cell(st, name, ids, k):
     return a[np.clip(ids, 0, a.shape[0] - 1), k]
 
 
+# (each check takes the mesh: tests/test_irregular_mesh.py runs them on 4- to 8-sided cells)
 def test_numpy_restatement_divergence_q9(x1_2562):
+    check_divergence_q9(x1_2562)
+
+
+def check_divergence_q9(mesh):
     """dynamics_tasks.rg:369-379 (Q9: s + u) restated with numpy"""
-    st = make_state(x1_2562, 5, "random")
+    st = make_state(mesh, 5, "random")
     O.Oracle(st).atm_compute_solve_diagnostics(0, 0)
     n, L = st.nCells, st.L
     ne = st["nEdgesOnCell"][:n, 0]
@@ -134,8 +139,12 @@ def test_numpy_restatement_divergence_q9(x1_2562):
 
 
 def test_numpy_restatement_vert_imp(x1_2562):
+    check_vert_imp(x1_2562)
+
+
+def check_vert_imp(mesh):
     """dynamics_tasks.rg:529-591 restated with numpy (vectorised over cells)"""
-    st = make_state(x1_2562, 5, "random")
+    st = make_state(mesh, 5, "random")
     ref = st.copy()
     O.Oracle(st).atm_compute_vert_imp_coefs(240.0)
     n, L = st.nCells, st.L
@@ -179,8 +188,12 @@ def test_numpy_restatement_vert_imp(x1_2562):
 
 
 def test_numpy_restatement_div_damping(x1_2562):
+    check_div_damping(x1_2562)
+
+
+def check_div_damping(mesh):
     """dynamics_tasks.rg:1736-1762 restated with numpy"""
-    st = make_state(x1_2562, 5, "random")
+    st = make_state(mesh, 5, "random")
     ref = st.copy()
     O.Oracle(st).atm_divergence_damping_3d(240.0)
     nE, L = st.nEdges, st.L
@@ -196,8 +209,12 @@ def test_numpy_restatement_div_damping(x1_2562):
 
 
 def test_numpy_restatement_output_diagnostics(x1_2562):
+    check_output_diagnostics(x1_2562)
+
+
+def check_output_diagnostics(mesh):
     """dynamics_tasks.rg:737-744 restated with numpy; theta untouched (:740 commented out)"""
-    st = make_state(x1_2562, 5, "random")
+    st = make_state(mesh, 5, "random")
     ref = st.copy()
     O.Oracle(st).atm_compute_output_diagnostics()
     n, L = st.nCells, st.L
@@ -209,9 +226,13 @@ def test_numpy_restatement_output_diagnostics(x1_2562):
 
 
 def test_numpy_restatement_reconstruct_2d(x1_2562):
+    check_reconstruct_2d(x1_2562)
+
+
+def check_reconstruct_2d(mesh):
     """dynamics_tasks.rg:1913-1947 restated with numpy (on a sphere and not)"""
     for sphere in (True, False):
-        st = make_state(x1_2562, 5, "random")
+        st = make_state(mesh, 5, "random")
         ref = st.copy()
         O.Oracle(st).mpas_reconstruct_2d(False, sphere)
         n, L = st.nCells, st.L
@@ -239,10 +260,14 @@ def test_numpy_restatement_reconstruct_2d(x1_2562):
 
 
 def test_restatement_recover_large_step(x1_2562):
+    check_recover_large_step(x1_2562)
+
+
+def check_recover_large_step(mesh, cells=range(40)):
     """dynamics_tasks.rg:1788-1870 restated with numpy (loops 1-2) and plain Python for the
     w recovery of the first 40 cells (the level-0 term added once per level iteration)"""
     for rk_step, ns in ((0, 2), (2, 3)):
-        st = make_state(x1_2562, 5, "random")
+        st = make_state(mesh, 5, "random")
         ref = st.copy()
         dt = 240.0
         O.Oracle(st).atm_recover_large_step_variables_work(ns, rk_step, dt)
@@ -271,7 +296,7 @@ def test_restatement_recover_large_step(x1_2562):
         assert np.array_equal(st["u"][:nE, :L], 2 * ru / (rz_full[c1, :L] + rz_full[c2, :L]))
         cf1, cf2, cf3 = ref["cf1"][0], ref["cf2"][0], ref["cf3"][0]
         fzm, fzp = ref["fzm"], ref["fzp"]
-        for c in range(40):
+        for c in cells:
             if ref["bdyMaskCell"][c, 0] > 5:
                 assert np.array_equal(st["w"][c, :L], w1[c])
                 continue

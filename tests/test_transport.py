@@ -40,9 +40,14 @@ def neighbourhood_bounds(st):
     return lo, hi
 
 
+# (each check takes the mesh: tests/test_irregular_mesh.py runs them on 4- to 8-sided cells)
 @pytest.mark.parametrize("L", [5, 56])
 def test_constant_preserved(x1_2562, L):
-    st, _ = transport_state(x1_2562, L, DT, const=0.0123)
+    check_constant_preserved(x1_2562, L)
+
+
+def check_constant_preserved(mesh, L):
+    st, _ = transport_state(mesh, L, DT, const=0.0123)
     out = run(st)
     s = out["scalars"][:st.nCells, :L]
     assert np.max(np.abs(s - 0.0123)) < 1e-12 * 0.0123 * 100
@@ -50,7 +55,11 @@ def test_constant_preserved(x1_2562, L):
 
 @pytest.mark.parametrize("L", [5, 56])
 def test_monotone_and_conservative(x1_2562, L):
-    st, vol = transport_state(x1_2562, L, DT)
+    check_monotone_and_conservative(x1_2562, L)
+
+
+def check_monotone_and_conservative(mesh, L):
+    st, vol = transport_state(mesh, L, DT)
     out = run(st)
     nC = st.nCells
     s_new = out["scalars"][:nC, :L]
@@ -69,10 +78,14 @@ def test_monotone_and_conservative(x1_2562, L):
 
 
 def test_unlimited_where_smooth(x1_2562):
+    check_unlimited_where_smooth(x1_2562)
+
+
+def check_unlimited_where_smooth(mesh):
     """a smooth field far from its extrema is transported by the high-order flux: the
     limited result differs from first-order upwind (the limiter does not reduce to it)"""
     L = 10
-    st, _ = transport_state(x1_2562, L, DT)
+    st, _ = transport_state(mesh, L, DT)
     nC = st.nCells
     lat = st["lat"][:nC, 0]
     st["scalars_old"][:nC, :L] = (0.01 + 0.005 * np.sin(2 * lat))[:, None, None] * np.ones((1, L, 8))

@@ -34,8 +34,13 @@ def mass(rho, vol, s):
 
 @pytest.mark.parametrize("L", [1, 2, 5, 56])
 def test_mono_rk_on_old_fluxes_matches_oracle(x1_2562, L):
+    check_mono_rk_on_old_fluxes_matches_oracle(x1_2562, L)
+
+
+# (each check takes the mesh: tests/test_irregular_mesh.py runs them on 4- to 8-sided cells)
+def check_mono_rk_on_old_fluxes_matches_oracle(mesh, L):
     """flux source = scalars_old: the oracle's monotonic task (1e-13 normwise)"""
-    st, _ = transport_state(x1_2562, L, DT)
+    st, _ = transport_state(mesh, L, DT)
     ref = st.copy()
     O.Oracle(ref).mpas_advance_scalars_mono(DT)
     got = R.advance_scalars_mono_rk(st, DT, flux_from_old=True)
@@ -52,7 +57,11 @@ def test_mono_rk_on_old_fluxes_matches_oracle(x1_2562, L):
 
 @pytest.mark.parametrize("L", [5, 56])
 def test_unlimited_stage_keeps_a_constant(x1_2562, L):
-    st, _ = transport_state(x1_2562, L, DT, const=0.0123)
+    check_unlimited_stage_keeps_a_constant(x1_2562, L)
+
+
+def check_unlimited_stage_keeps_a_constant(mesh, L):
+    st, _ = transport_state(mesh, L, DT, const=0.0123)
     st["scalars"][...] = st["scalars_old"]
     st["rho_zz"][...] = 1.0  # (not read: rho_int is the stage's own density)
     out, _ = R.advance_scalars(st, DT)
@@ -65,7 +74,11 @@ def test_unlimited_stage_keeps_a_constant(x1_2562, L):
 
 @pytest.mark.parametrize("L", [5, 56])
 def test_unlimited_stage_conserves_and_overshoots(x1_2562, L):
-    st, vol = transport_state(x1_2562, L, DT)
+    check_unlimited_stage_conserves_and_overshoots(x1_2562, L)
+
+
+def check_unlimited_stage_conserves_and_overshoots(mesh, L):
+    st, vol = transport_state(mesh, L, DT)
     st["scalars"][...] = st["scalars_old"]
     nC = st.nCells
     out, r_i = R.advance_scalars(st, DT)
@@ -82,7 +95,11 @@ def test_unlimited_stage_conserves_and_overshoots(x1_2562, L):
 
 @pytest.mark.parametrize("L", [5, 56])
 def test_rk3_transport_is_monotone_and_conservative(x1_2562, L):
-    st, vol = transport_state(x1_2562, L, DT)
+    check_rk3_transport_is_monotone_and_conservative(x1_2562, L)
+
+
+def check_rk3_transport_is_monotone_and_conservative(mesh, L):
+    st, vol = transport_state(mesh, L, DT)
     st["scalars"][...] = st["scalars_old"]
     nC = st.nCells
     out = R.rk3_transport(st, DT)
@@ -102,7 +119,11 @@ def test_rk3_transport_is_monotone_and_conservative(x1_2562, L):
 
 
 def test_three_unlimited_stages_are_third_order(x1_2562):
-    st0 = R.stream_flow_state(x1_2562, make_state)
+    check_three_unlimited_stages_are_third_order(x1_2562)
+
+
+def check_three_unlimited_stages_are_third_order(mesh):
+    st0 = R.stream_flow_state(mesh, make_state)
     nC, L = st0.nCells, st0.L
 
     def run_steps(N, dt):
