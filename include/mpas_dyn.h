@@ -197,6 +197,15 @@ int mpas_get_stream(mpas_ctx* ctx, void** stream);
  * graph are the same for both.  Read-only "dynkeep_fresh": the flag (1: the columns hold the running sequence's
  * values; a full step clears it).  Every field bit-identical; 0: the plain kernels.  Any other value:
  * MPAS_EINVAL.
+ * "tukeep" = 1 (default; speed only; where "dynkeep" is active, in steps without per-task timing): between two steps at "stepkeep_gen" 2
+ * the last stage's dyn_tend edge kernel stores other bits at one level of one column only -- tend_u below the
+ * top, which reads w at the top -- so with the flag 1 its guarded instance returns and one small kernel behind
+ * it, in the same task, forms that level from tend_u_euler as stored; stage 0's edge kernel then leaves
+ * tend_u_euler alone.  With the flag 0 every launch works as under "dynkeep" alone.  The same launches, timing
+ * keys and captured graph.  A step with
+ * per-task timing on makes "dynkeep"'s launches, so that its dyn_tend rows time the task's whole work.
+ * Read-only "tukeep_active": 1 where a kept step of this context would take that form now.
+ * Every field bit-identical; 0: "dynkeep"'s launches.  Any other value: MPAS_EINVAL.
  * "trepw" = 2 (speed only; measured within 2 %, default 1): two
  * edges per wavefront in the transport's edge kernel.  "trtile" = 1
  * (speed only, default 0) runs the transport as two tiled kernels with the scalars of

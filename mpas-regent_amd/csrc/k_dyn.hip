@@ -298,16 +298,26 @@ __global__ __launch_bounds__(256) void k_dyn_cp_orph(DevState S) {
 // kernel stores is a function of fields no task of the step writes, but stage 2's edge kernel adds the deferred
 // del4 to tend_u_euler in place.  X_dkf 0: the kernel as without DK, its tend_u_euler also stored to X_tue0 (the
 // same lanes and padding); 1: tend_u_euler = X_tue0 at every level but L, nothing else -- delsq_u is in place
+// TK (atm_srk3 option "tukeep", with DK): in a fresh kept step tend_u_euler, v and every level of
+// tend_u but L - 1 hold the step-before's bits, and X_F has no reader.  Stage 0's instance, X_dkf 1: nothing --
+// tend_u_euler keeps its final value, del4 included, and no task before stage 2's edge kernels reads it.  Stage
+// 2's instance (the DIN form, HF, with the flux), X_dkf 1: nothing either; k_dyn_B_top behind it forms tend_u at
+// level L - 1.  X_dkf 0: both as without TK.  The flag is tested before anything else is live
 template <int LP, bool RK0, bool MD, bool HF, bool DIN = false, bool NOF = false, bool NTU = false, bool NCP = false,
-          bool DK = false>
+          bool DK = false, bool TK = false>
 __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState S, DynK a) {
     static_assert(!NTU || !MD, "the dead tend_u: reference semantics");
     static_assert(!NCP || (RK0 && NOF && NTU), "u and ru dead at the edge: no tend_u, no flux, no rk > 0 perturbation flux");
-    static_assert(!DK || (NCP && HF), "the kept tend_u_euler: stage 0 of a kept step, fast path");
+    static_assert(!DK || (NCP && HF) || (TK && DIN && HF && !MD && !NOF && !NTU),
+                  "the kept tend_u_euler: stage 0 of a kept step, fast path; with TK also stage 2's");
+    static_assert(!TK || DK, "the kept tend_u: a guarded instance");
+    if constexpr (TK) {
+        if (dk_fresh(S)) return;
+    }
     ColMap<LP> m(S, KE);
     const int L = S.L, k = m.k, e = m.ent;
     if (e >= S.nEO) return;
-    if constexpr (DK) {
+    if constexpr (DK && !TK) {
         if (dk_fresh(S)) {
             if (k != L) colk(fw(S, F_tend_u_euler), e) = colk(fd(S, X_tue0), e);
             return;
@@ -681,6 +691,78 @@ __global__ __launch_bounds__(256, LP == 64 && DIN ? 4 : 1) void k_dyn_B(DevState
         tend_u += tue + tr_phys;  // :1161-1163
         if (!NTU) colk(fw(S, F_tend_u), e) = PADW(tend_u);
     }
+}
+
+// option "tukeep" (atm_srk3, a kept step's stage 2, right behind k_dyn_B TK): tend_u at level
+// L - 1, the one level of the one column of that kernel's stores that differs from the step before -- tend_u(k)
+// reads the evolving set through w at level k + 1 alone (the curvature term), and of w only level L moves.  One
+// lane per owned edge.  X_dkf 0: nothing (k_dyn_B TK has just stored the whole column).  X_dkf 1: k_dyn_B's own
+// statements at k = L - 1 in its order on the same operands -- what its lanes k - 1 and k + 1 hold for the
+// shuffles is loaded here (u below, w and the stored wduz at level L) -- with tend_u_euler taken as stored: it
+// carries its del4 part, so none of DIN's arithmetic.  The one double is stored; nothing else is
+template <int LP>
+__global__ __launch_bounds__(256) void k_dyn_B_top(DevState S, DynK a) {
+    if (!dk_fresh(S)) return;
+    const int L = S.L, k = L - 1;
+    const int e = (int)(blockIdx.x * 256u + threadIdx.x) + S.lo[KE];
+    if (e >= S.nEO || k < 0) return;
+    int rec[24];
+    row_ld(fi(S, X_eB) + (size_t)e * 24, rec);
+    const int cell1 = rec[0], cell2 = rec[1], neoe = rec[21];
+    const double *u_f = fd(S, F_u), *pv_f = fd(S, F_pv_edge), *w_f = fd(S, F_w);
+    const int* eoe = fi(S, F_edgesOnEdge) + (size_t)e * 20;
+    const double* woe = fd(S, F_weightsOnEdge) + (size_t)e * 20;
+    // every load first (the padding ids of the QF slots are valid edges, as in k_dyn_B)
+    int ee_[QF];
+    double ue_[QF], pve_[QF], woe_[QF];
+#pragma unroll
+    for (int j = 0; j < QF; j++) ee_[j] = rec[2 + j];
+    row_ld(woe, woe_);
+#pragma unroll
+    for (int j = 0; j < QF; j++) {
+        ue_[j] = colk(u_f, ee_[j]);
+        pve_[j] = colk(pv_f, ee_[j]);
+    }
+    const double u = colk(u_f, e), u_m = k == 0 ? 0.0 : at_off(u_f, col_off<LP>(e, k - 1));  // (lvl_dn: 0.0 below level 0)
+    const double rw1 = colk(fd(S, F_rw), cell1), rw2 = colk(fd(S, F_rw), cell2);
+    const double w1 = colk(w_f, cell1), w2 = colk(w_f, cell2);
+    const double w1p = at_off(w_f, col_off<LP>(cell1, L)), w2p = at_off(w_f, col_off<LP>(cell2, L));
+    const double rho_edge = colk(fd(S, F_rho_edge), e), pv = colk(pv_f, e);
+    const double ke1 = colk(fd(S, F_ke), cell1), ke2 = colk(fd(S, F_ke), cell2);
+    const double hd1 = colk(fd(S, F_h_divergence), cell1), hd2 = colk(fd(S, F_h_divergence), cell2);
+    const double tue = colk(fd(S, F_tend_u_euler), e), tr_phys = colk(fd(S, F_tend_ru_physics), e);
+    const double wduzL = fd(S, F_wduz)[(size_t)e * LP + lpos(LP, L)];
+    const double invDc = fd(S, F_invDcEdge)[e];
+    const double fzm = fd(S, F_fzm)[k], fzp = fd(S, F_fzp)[k], rdzw = fd(S, F_rdzw)[k];
+    // ---- wduz (:972-980): at k = L - 1 B's first form (its flux3 form needs 1 < k < L - 1), level L as stored
+    double wduz = 0.0;
+    if (k == 1 || k == L - 1) wduz = 0.5 * (rw1 + rw2) * (fzm * u + fzp * u_m);
+    const double wduz_p = wduzL;
+    // ---- tend_u (:987-1007)
+    double tend_u = -rdzw * (wduz_p - wduz);
+    double q = 0.0;
+    const double dL = (double)L;  // Q10 value, nVertLevels * term
+#pragma unroll
+    for (int j = 0; j < QF; j++) {
+        double workpv = 0.5 * (pv + pve_[j]);
+        q = add_if(j < neoe, q, (woe_[j] * ue_[j] * workpv) * dL);
+    }
+    for (int j = QF; j < neoe; j++) {
+        double workpv = 0.5 * (pv + colk(pv_f, eoe[j]));
+        q += (woe[j] * colk(u_f, eoe[j]) * workpv) * dL;
+    }
+    tend_u += rho_edge * (q - (ke2 - ke1) * invDc) - u * 0.5 * (hd1 + hd2);
+    {  // curvature (:1011-1017, Q12 literal)
+        const double cosA = ldc(fd(S, X_cosAngleEdge) + e), cosL = ldc(fd(S, X_cosLatEdge) + e);
+        const double cA = (2.0 * kOmega * cosA * cosL * rho_edge * 0.25 * (w1 + w1p + w2 + w2p));
+        const double cB = (u * 0.25 * (w1 + w1p + w2 + w2p) * rho_edge * a.inv_r_earth);
+        tend_u -= cA - cB;
+    }
+    // ---- Rayleigh damping (:1152-1159)
+    if (a.rayleigh && k > L - kRayleighLevels + 1)
+        tend_u -= rho_edge * u * (((double)k - (double)(L - kRayleighLevels)) * a.rayleigh_inv);
+    tend_u += tue + tr_phys;  // :1161-1163 (tue: the tend_u_euler read)
+    colk(fw(S, F_tend_u), e) = tend_u;
 }
 
 // option "bsplit" (fast path): B's per-edge theta flux H = ru F (+ dvEdge (ru_save - ru)
@@ -1666,9 +1748,20 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
     const bool dk = in.dynkeep != 0;
     if (dk && (MD || !hf || et || S.halo || in.smlE || in.hfuse || (rk0 && !(in.keptA && a.d4o && ntu && nth))))
         return hipErrorInvalidValue;
+    // (in.tukeep, atm_srk3 option tukeep, stages 0 and 2 of a kept step: k_dyn_B TK, and behind stage 2's
+    // k_dyn_B_top -- the last stage's whole edge kernel in its d4i form, nothing else of it live but v)
+    const bool tk = in.tukeep != 0;
+    if (tk && (!dk || (!rk0 && (!din || ntu || nth || a.tme || a.cp || a.rud != 0.0)))) return hipErrorInvalidValue;
     auto kB = [&](const DevState& X) {
         const int nb = col_blocks<LP>(X, KE);
         if (!nb) return;
+        if constexpr (!MD) {
+            if (tk && !rk0) {  // (ahead of option bsplit: its flux kernel is part of what a fresh pass leaves out)
+                k_dyn_B<LP, false, false, true, true, false, false, false, true, true><<<nb, 256, 0, st>>>(X, a);
+                k_dyn_B_top<LP><<<(X.nEO - X.lo[KE] + 255) / 256, 256, 0, st>>>(X, a);
+                return;
+            }
+        }
         if (et) {
             if (hf) {
                 if (rk0) k_dyn_B<LP, true, MD, true, false, true><<<nb, 256, 0, st>>>(X, a);
@@ -1692,7 +1785,8 @@ static hipError_t dyn_lp_md(const DevState& S, hipStream_t st, const DynTendArgs
                         if (a.cpA) {  // (the copies made by A: NCP)
                             if constexpr (decltype(H)::value) {
                                 if (dk) {
-                                    k_dyn_B<LP, true, false, true, false, true, true, true, true><<<nb, 256, 0, st>>>(X, a);
+                                    if (tk) k_dyn_B<LP, true, false, true, false, true, true, true, true, true><<<nb, 256, 0, st>>>(X, a);
+                                    else k_dyn_B<LP, true, false, true, false, true, true, true, true><<<nb, 256, 0, st>>>(X, a);
                                     return;
                                 }
                             }

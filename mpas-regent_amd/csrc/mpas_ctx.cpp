@@ -214,6 +214,14 @@ struct mpas_ctx {
     // instances load, cleared by every full step and set by every kept one, so one captured graph serves both.
     // Invalidation is keep_gen's: an outside call leads to a full step, which clears the flag first
     int dynkeep = 1;
+    // option "tukeep" (exactly where dynkeep is active): between two kept steps stage 2's edge
+    // kernel stores other bits at one level of one column only -- tend_u at level L - 1, which reads w at level L;
+    // tend_u_euler (final, del4 included), v and the rest of tend_u hold the step-before's, and its flux X_F has no
+    // reader in a fresh kept step.  With X_dkf 1 the guarded instance of that kernel returns and k_dyn_B_top,
+    // launched behind it in the same task, forms that one level from tend_u_euler as stored; stage 0's guarded edge
+    // kernel then returns without copying X_tue0 back.  X_dkf 0: every launch as with dynkeep alone.  The same
+    // launches either way: one captured graph, dynkeep's timing keys.  Invalidation is keep_gen's
+    int tukeep = 1;
     int keep_gen = 0;
     double keep_dt = 0.0;
     int keep_schedule = -1;
@@ -1036,7 +1044,7 @@ struct StepForm {
     int tme, hf, ddx, fluxf, aco;
     bool defer4, d4_pending, mru, msml, md_fold;
     bool early_state_dead, early_diag_dead, solve0_dead, norz;
-    bool stepkeep, vik, a0k, dk, kept, keep2;
+    bool stepkeep, vik, a0k, dk, tuk, kept, keep2;
 };
 
 StepForm step_form(const mpas_ctx* c, double dt, int schedule, int gen) {
@@ -1146,6 +1154,12 @@ StepForm step_form(const mpas_ctx* c, double dt, int schedule, int gen) {
     // E, which decide on X_dkf; a full step clears the flag (in its setup task), a kept one sets it after stage
     // 2's E (in that dyn_tend task): no timing key of its own.  (stepkeep = 2 skips those launches on the host)
     f.dk = c->dynkeep && f.a0k && c->stepkeep == 1;
+    // option tukeep: the kept steps' stage-0 and stage-2 edge kernels in their TK instances, k_dyn_B_top behind the
+    // latter -- the decision is X_dkf's too (no flag, capture, timing key or scratch column of its own)
+    // Not while per-task timing is on: a timed step is the one whose dyn_tend rows are set against the reference
+    // task's B_alg (bench.py's roofline record), so its launches do that task's work -- dynkeep's instances, which
+    // leave every field and X_tue0 as the TK ones expect to find them (either form may follow the other)
+    f.tuk = c->tukeep && f.dk && !c->timing;
     f.kept = gen >= 1;
     // option stepkeep = 2, generation 2: everything stage 0's dyn_tend stores is in place from the
     // generation-1 step (whose stage 0 read the diagnostics the step itself formed, as this one would)
@@ -1298,6 +1312,9 @@ DynTendArgs stage_dyn_tend(mpas_ctx* c, const StepForm& f, StepRun& r, int s) {
     // the plain ones and fills X_tue0 / X_w0..2, the later ones copy those back (the same launches: one graph)
     const bool dkept = f.dk && f.kept;
     if (dkept) a.dynkeep = s + 1;
+    // option tukeep: stage 0's guarded edge kernel leaves tend_u_euler alone in a fresh pass, stage 2's forms
+    // nothing there and k_dyn_B_top tend_u's level L - 1 (stage 1 launches no edge kernel in a kept step)
+    if (dkept && f.tuk && s != 1) a.tukeep = 1;
     if (f.keep2 && s == 0) {  // (w below level L from the generation-1 step's copy; nothing else to form)
         run_task(c, "stepkeep_restore_w", [&] { return launch_cell_col_copy(S, st, X_w0, F_w); });
     } else {
@@ -1750,6 +1767,7 @@ const OptRow kOptions[] = {
     opt("vikeep", &mpas_ctx::vikeep, O_RANGE, 0, 1, "vikeep must be 0 or 1"),
     opt("a0keep", &mpas_ctx::a0keep, O_RANGE, 0, 1, "a0keep must be 0 or 1"),
     opt("dynkeep", &mpas_ctx::dynkeep, O_RANGE, 0, 1, "dynkeep must be 0 or 1"),
+    opt("tukeep", &mpas_ctx::tukeep, O_RANGE, 0, 1, "tukeep must be 0 or 1"),
     opt("mru", &mpas_ctx::mru, O_BOOL),
     opt("msml", &mpas_ctx::msml, O_BOOL),
     opt("vdyn", &mpas_ctx::vdyn, O_BOOL),
@@ -1873,6 +1891,7 @@ const OptRow kOptions[] = {
         hipcheck(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
         return fresh;
     }),
+    query("tukeep_active", [](mpas_ctx* c) -> int64_t { return step_form(c, 0.0, 1, 0).tuk; }),  // (its kept steps' form)
     query("eoe_same", [](mpas_ctx* c) -> int64_t { return prepare_now(c), c->S.eoe_same; }),
     // (the switches of the step's form that do not depend on dt, schedule or generation)
     query("hfuse_active", [](mpas_ctx* c) -> int64_t { return step_form(c, 0.0, 1, 0).hf; }),

@@ -262,6 +262,11 @@ struct DynTendArgs {
     // Only the forms a kept step launches (keptA at stage 0, the fast path, undecomposed): any other
     // hipErrorInvalidValue
     int dynkeep = 0;
+    // option "tukeep" (with dynkeep, stages 0 and 2 of a kept step): X_dkf 1 -- stage 0's edge
+    // kernel leaves tend_u_euler as it stands (final, del4 included), stage 2's returns and k_dyn_B_top behind it
+    // forms tend_u at level L - 1 alone; X_dkf 0: the call as with dynkeep alone.  Stage 2's call must be the d4i
+    // form with its flux and tend_u live (any other: hipErrorInvalidValue)
+    int tukeep = 0;
 };
 
 enum EntityKind { KC = 0, KE = 1, KV = 2 };  // DevState::lo index
