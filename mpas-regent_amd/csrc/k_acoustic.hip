@@ -91,8 +91,12 @@ __global__ __launch_bounds__(256) void k_acoustic_orph(DevState S, double coefp)
 // alone), no half of a 16-B load dead.  The expressions stay as written, with dd = 0.0 (0.0 - E is not -E for
 // E = +0.0; no contraction, no fast-math).  A template parameter, not a third value of the runtime ddx: the
 // kernels without it are then the ones they were, register for register
+// NST (atm_srk3 option ntu: the launches with wold bit 1, two per step): the substep's four state columns are
+// dead, so nothing of them is stored and wwAvg, which only its own store reads, is not loaded -- rw_p comes by
+// itself.  The same reason makes it a template parameter, for the one combination atm_srk3's default step
+// launches (fast path, MODE 2, not FIRST, ACO, DD0); every other launch with wold bit 1 takes the runtime test
 template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO = false,
-          bool DD0 = false>
+          bool DD0 = false, bool NST = false>
 __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int small_step, double epssm, double resm,
                                               double coefp, int ncb, Blk bk, int wold = 1, int ddx = 0,
                                               double dtseps = 0.0) {
@@ -102,6 +106,7 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     static_assert(!(TME && ACO), "option tmedge keeps the stored set (its exact first launch would lose a wave)");
     static_assert(!SML || (FIRST && !MPASV), "set_smlstep precedes a stage's first substep (reference semantics)");
     static_assert(SML != 2 || !EXACT, "the flux sum reassociates: fast path only");
+    static_assert(!NST || (!EXACT && !FIRST && MODE == 2 && !TME && ACO && DD0), "the default step's -st launch");
     const int L = S.L, k = (int)(threadIdx.x % LP);
     int blk = bk.b;
     blk = xcd_block_n(S.xcd, blk, ncb);  // (ncb: the cell blocks, bk.n or fewer)
@@ -113,6 +118,10 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     double* rwp_f = fw(S, F_rw_p);
     double* ww_f = fw(S, F_wwAvg);
     const bool kl = k < L;
+    // The cache policy of the launch's own columns (mpas_dev.h MPAS_NT): N1 the invariant
+    // columns, N2 the state columns, N3 the column stores.  theta_m is both an own column and the other
+    // cells' gather, so its pair with tend_rho stays on the default policy; so does every gather.
+    constexpr bool N1 = nt_group(1), N2 = nt_group(2), N3 = nt_group(4);
     // ---- every load of the column and of its edge gathers first, ahead of the first
     // store (which could alias them for the compiler)
     const double spec = fd(S, F_specZoneMaskCell)[c];
@@ -133,13 +142,14 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     if constexpr (FIRST) {
         rtp = rpp = rwp = ww = 0.0;
     } else {
-        col_rd2<LP>(rtp_f, rpp_f, c, k, L, rtp, rpp);
-        col_rd2<LP>(rwp_f, ww_f, c, k, L, rwp, ww);
+        col_rd2<LP, N2>(rtp_f, rpp_f, c, k, L, rtp, rpp);
+        if constexpr (NST) rwp = col_rd<LP, N2>(rwp_f, c, k, L), ww = 0.0;  // (wwAvg: dead, not loaded)
+        else col_rd2<LP, N2>(rwp_f, ww_f, c, k, L, rwp, ww);
     }
     col_rd2<LP>(fd(S, F_theta_m), fd(S, F_tend_rho), c, k, L, tm, tend_rho);
     // SML: the point's cprMask byte with the column loads (tested after a lane condition it
     // was loaded under a divergent branch and waited for there)
-    const uint8_t cpr = SML ? ((const uint8_t*)S.f[F_cprMask])[p] : 0;
+    const uint8_t cpr = SML ? ld_off<N1>((const uint8_t*)S.f[F_cprMask], (uint32_t)p) : 0;
     static_assert(NF % 2 == 0, "slot pairs");
 #pragma unroll
     for (int i = 0; i < NF; i += 2) {
@@ -185,15 +195,15 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     }
     // (rup_ / ts_ at k >= L: unused, the flux sum below selects on kl)
     // (ACO: w with dss -- with rw under !ddx; alone under DD0, where dss pairs with alpha_tri, below)
-    if constexpr (!ACO) col_rd2<LP>(fd(S, F_w), fd(S, F_coftz), c, k, L, w, coftz);
-    else if constexpr (DD0) w = col_rd<LP>(fd(S, F_w), c, k, L);
-    else if (ddx) col_rd2<LP>(fd(S, F_w), fd(S, F_dss), c, k, L, w, dss);
-    else col_rd2<LP>(fd(S, F_w), fd(S, F_rw), c, k, L, w, rw);
-    col_rd2<LP>(fd(S, F_zz), fd(S, F_rho_zz), c, k, L, zz, rz);
+    if constexpr (!ACO) col_rd2<LP, N1>(fd(S, F_w), fd(S, F_coftz), c, k, L, w, coftz);
+    else if constexpr (DD0) w = col_rd<LP, N1>(fd(S, F_w), c, k, L);
+    else if (ddx) col_rd2<LP, N1>(fd(S, F_w), fd(S, F_dss), c, k, L, w, dss);
+    else col_rd2<LP, N1>(fd(S, F_w), fd(S, F_rw), c, k, L, w, rw);
+    col_rd2<LP, N1>(fd(S, F_zz), fd(S, F_rho_zz), c, k, L, zz, rz);
     const double fzm = fd(S, F_fzm)[k], fzp = fd(S, F_fzp)[k];
     int wst = 0;  // SML: set_smlstep's w store (1: the new w, 2: the padding's 0.0), made below
     if constexpr (SML == 2) {  // (X_smlS: k_sml_flux's sum of the slope fluxes)
-        double wn = w - colk(fd(S, X_smlS), c);
+        double wn = w - colk_ld(N1, fd(S, X_smlS), c);
         wn *= (fzm * zz + fzp * lvl_dn<LP>(zz, k));
         const bool rz_ok = fi(S, F_bdyMaskCell)[c] <= kRelaxZone;
         wst = ((k <= L) & rz_ok & (cpr != 0)) ? 1 : ((k > L) & rz_ok) ? 2 : 0;
@@ -246,21 +256,21 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     // the w tendency: the state w in the reference and under physics = 1 (Q8), tend_w under
     // the MPAS dynamics (physics = 2); the implicit Rayleigh term reads the state w
     const double tw = (MPASV && S.physics == 2) ? col_rd<LP>(fd(S, F_tend_w), c, k, L) : w;
-    col_rd2<LP>(fd(S, F_cofwt), fd(S, F_cofwz), c, k, L, cofwt, cofwz);
-    if constexpr (!ACO) col_rd2<LP>(fd(S, F_cofwr), fd(S, F_a_tri), c, k, L, cofwr, a_tri);
+    col_rd2<LP, N1>(fd(S, F_cofwt), fd(S, F_cofwz), c, k, L, cofwt, cofwz);
+    if constexpr (!ACO) col_rd2<LP, N1>(fd(S, F_cofwr), fd(S, F_a_tri), c, k, L, cofwr, a_tri);
     // (ddx, atm_srk3 with option smlsum: rw_save - rw, the step uses only their difference, from
     // X_Dd -- formed once per step, the same value: one column read instead of two)
     double dd;
     if constexpr (DD0) {
-        col_rd2<LP>(fd(S, F_alpha_tri), fd(S, F_dss), c, k, L, alpha, dss);
+        col_rd2<LP, N1>(fd(S, F_alpha_tri), fd(S, F_dss), c, k, L, alpha, dss);
         dd = 0.0;
     } else if (!MPASV && ddx) {
-        col_rd2<LP>(fd(S, F_alpha_tri), fd(S, X_Dd), c, k, L, alpha, dd);
-        if constexpr (!ACO) dss = col_rd<LP>(fd(S, F_dss), c, k, L);
+        col_rd2<LP, N1>(fd(S, F_alpha_tri), fd(S, X_Dd), c, k, L, alpha, dd);
+        if constexpr (!ACO) dss = col_rd<LP, N1>(fd(S, F_dss), c, k, L);
     } else {
-        col_rd2<LP>(fd(S, F_alpha_tri), fd(S, F_rw_save), c, k, L, alpha, rws);
-        if constexpr (!ACO) col_rd2<LP>(fd(S, F_rw), fd(S, F_dss), c, k, L, rw, dss);
-        else dss = col_rd<LP>(fd(S, F_dss), c, k, L);
+        col_rd2<LP, N1>(fd(S, F_alpha_tri), fd(S, F_rw_save), c, k, L, alpha, rws);
+        if constexpr (!ACO) col_rd2<LP, N1>(fd(S, F_rw), fd(S, F_dss), c, k, L, rw, dss);
+        else dss = col_rd<LP, N1>(fd(S, F_dss), c, k, L);
         dd = rws - rw;
     }
     double gam = 0.0, tend_th = 0.0;
@@ -278,7 +288,7 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         double* rup_out = fw(S, X_rupB);
 #pragma unroll
         for (int i = 0; i < NF; i++)
-            if ((own >> i) & 1) colk(rup_out, e_[i]) = PADW(rup_[i]);  // (level L: the value read)
+            if ((own >> i) & 1) colk_st(N3, rup_out, e_[i], PADW(rup_[i]));  // (level L: the value read)
     }
     if constexpr (SML != 0) {
         if (wst == 1) {
@@ -294,12 +304,12 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     // wold bit 1 (atm_srk3 option ntu, MODE != 0: the last substep of a stage before the step's last):
     // this substep's rho_pp, rtheta_pp, rw_p and wwAvg are dead -- the next stage's first substep sets
     // them (:1615-1636) before any task reads them, and the damping reads this substep's div (X_dvA)
-    const bool nst = MODE != 0 && (wold & 2);
+    const bool nst = NST || (MODE != 0 && (wold & 2));
     // (level L: the kept value, keep tails in mpas_dev.h -- every line of the column whole)
     if (MODE == 0 || (wold & 1)) colk(fw(S, F_rtheta_pp_old), c) = KEEPW(rtpo, keepv<LP>(S, F_rtheta_pp_old, KC, c));
     // MODE 1/2: this substep's div (:1755) for the damping applied by the next substep
     auto store_div = [&](double rtp_new) {
-        if constexpr (MODE != 0) colk(fw(S, X_dvA), c) = kl ? -(rtp_new - rtpo) : 0.0;
+        if constexpr (MODE != 0) colk_st(N3, fw(S, X_dvA), c, kl ? -(rtp_new - rtpo) : 0.0);
     };
     if (small_step == 0) {
         ww = 0;
@@ -318,7 +328,7 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
         const bool on = kl & (e < S.nEdges) & !(sh1 & sh2);
         rpe = damp_edge<LP>(rpe, colk(fd(S, X_dvB), x1), colk(fd(S, X_dvB), x2), colk(tm_f, x1) + colk(tm_f, x2),
                             fd(S, F_specZoneMaskEdge)[e], coefp, on);
-        if ((own >> i) & 1) colk(fw(S, X_rupB), e) = PADW(rpe);
+        if ((own >> i) & 1) colk_st(N3, fw(S, X_rupB), e, PADW(rpe));
         return rpe;
     };
 
@@ -335,10 +345,10 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
             ww = ww + 0.5 * (1.0 + epssm) * rwp;
         }
         if (!nst) {
-            colk(rpp_f, c) = KEEPW(rpp, keepv<LP>(S, F_rho_pp, KC, c));
-            colk(rtp_f, c) = KEEPW(rtp, keepv<LP>(S, F_rtheta_pp, KC, c));
-            colk(rwp_f, c) = PADW(rwp);
-            if (!(MPASV && (wold & 2))) colk(ww_f, c) = PADW(ww);  // (MPASV, wold bit 1: wwAvg dead)
+            colk_st(N3, rpp_f, c, KEEPW(rpp, keepv<LP>(S, F_rho_pp, KC, c)));
+            colk_st(N3, rtp_f, c, KEEPW(rtp, keepv<LP>(S, F_rtheta_pp, KC, c)));
+            colk_st(N3, rwp_f, c, PADW(rwp));
+            if (!(MPASV && (wold & 2))) colk_st(N3, ww_f, c, PADW(ww));  // (MPASV, wold bit 1: wwAvg dead)
         }
         store_div(rtp);
         return;
@@ -509,17 +519,18 @@ __device__ __forceinline__ void acoustic_body(const DevState& S, double dts, int
     // (paired 16-B stores, every lane; level L of rho_pp / rtheta_pp keeps its value)
     const double rtp_new = ts - rdzw * (coftz_p * rwp_p - coftz * x);
     if (!nst) {
-        put2f<LP>(rpp_f, c, rtp_f, c, k, KEEPW(rs - cofrz * (rwp_p - x), keepv<LP>(S, F_rho_pp, KC, c)),
-                 KEEPW(rtp_new, keepv<LP>(S, F_rtheta_pp, KC, c)));
-        put2f<LP>(rwp_f, c, ww_f, c, k, PADW((k < L) ? x : rwp), PADW(ww));
+        put2f<LP, N3>(rpp_f, c, rtp_f, c, k, KEEPW(rs - cofrz * (rwp_p - x), keepv<LP>(S, F_rho_pp, KC, c)),
+                     KEEPW(rtp_new, keepv<LP>(S, F_rtheta_pp, KC, c)));
+        put2f<LP, N3>(rwp_f, c, ww_f, c, k, PADW((k < L) ? x : rwp), PADW(ww));
     }
     store_div(rtp_new);
 }
-template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO, bool DD0>
+template <int LP, bool EXACT, bool SELF, bool FIRST, bool MPASV, int MODE, bool TME, int SML, bool ACO, bool DD0,
+          bool NST = false>
 __global__ __launch_bounds__(256) void k_acoustic(DevState S, double dts, int small_step, double epssm, double resm,
                                                  double coefp, int ncb, int wold, int ddx, double dtseps) {
-    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML, ACO, DD0>(S, dts, small_step, epssm, resm, coefp, ncb,
-                                                                          this_blk(), wold, ddx, dtseps);
+    acoustic_body<LP, EXACT, SELF, FIRST, MPASV, MODE, TME, SML, ACO, DD0, NST>(S, dts, small_step, epssm, resm, coefp,
+                                                                               ncb, this_blk(), wold, ddx, dtseps);
 }
 // MODE 2 on a small grid (fewer than kTailCells owned cells, where a launch's fixed cost is
 // most of its time): the orphan edges' blocks at the tail of the cell grid, one launch
@@ -742,6 +753,13 @@ static hipError_t acoustic_lp(const DevState& S, hipStream_t st, double dts, int
                     if (tme) sml ? MPAS_AC(true, false, M, true, 1) : MPAS_AC(true, false, M, true, 0);
                     else sml ? MPAS_AC(true, false, M, false, 1) : MPAS_AC(true, false, M, false, 0);
                 } else {
+                    if constexpr (M == 2 && !E && A && D) {  // (the default step's -st launch: NST)
+                        if (!tme && (wold & 2)) {
+                            k_acoustic<LP, false, SF, false, false, 2, false, 0, true, true, true>
+                                <<<grid, 256, 0, st>>>(X, dts, small_step, epssm, resm, coef_prev, ncb, wold, 0, dtseps);
+                            return;
+                        }
+                    }
                     if (tme) MPAS_AC(false, false, M, true, false);
                     else MPAS_AC(false, false, M, false, false);
                 }

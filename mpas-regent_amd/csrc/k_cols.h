@@ -636,10 +636,11 @@ __device__ __forceinline__ void setup_vi_body(const DevState& S, int ncb, double
         const int c = col_of<LP>(xcd_block_n(S.xcd, blk, ncb)) + S.lo[KC];
         if (c >= S.nCO) return;
         double w, a, b, cc, alpha, gamma, gamma_old, kd = 0.0;
-        gather2<LP>(fd(S, F_w), c, fd(S, X_a0), c, k, w, a);
-        gather2<LP>(fd(S, X_b0), c, fd(S, X_c0), c, k, b, cc);
-        if constexpr (KD) gather2<LP>(fd(S, F_gamma_tri), c, fd(S, X_kd0), c, k, gamma_old, kd);
-        else gamma_old = colk(fd(S, F_gamma_tri), c);
+        constexpr bool NT = nt_group(8);  // (own columns, read once: mpas_dev.h MPAS_NT)
+        gather2<LP, NT>(fd(S, F_w), c, fd(S, X_a0), c, k, w, a);
+        gather2<LP, NT>(fd(S, X_b0), c, fd(S, X_c0), c, k, b, cc);
+        if constexpr (KD) gather2<LP, NT>(fd(S, F_gamma_tri), c, fd(S, X_kd0), c, k, gamma_old, kd);
+        else gamma_old = colk_ld(NT, fd(S, F_gamma_tri), c);
         vi_alpha_gamma<LP>(a, b, cc, gamma_old, k, alpha, gamma);
         put2f<LP>(fw(S, F_w_2), c, fw(S, F_alpha_tri), c, k, KEEPW(w, keepv<LP>(S, F_w_2, KC, c)),
                   vi_alpha_st<LP>(S, c, k, alpha));

@@ -691,6 +691,49 @@ template <int LP>
 __device__ __forceinline__ uint32_t col_off(int ent, int k) {
     return ((uint32_t)ent * (uint32_t)LP + (uint32_t)lpos(LP, k)) * (uint32_t)sizeof(double);
 }
+// Streamed (non-temporal) loads and stores, for bytes a launch touches once: a column-per-wavefront kernel's own
+// columns pass through the 4 MiB L2 once per launch, and with the default policy they evict the lines the
+// neighbour gathers re-read there.  The NT forms of the helpers below (a policy template argument, false =
+// the plain form) load or store the same address through __builtin_nontemporal_load / _store -- the same
+// bits -- and go through the same bounds check.  Which groups of accesses use them is fixed at build time, the
+// bits of MPAS_NT: 1 the acoustic launch's own invariant columns, 2 its own state columns, 4 its
+// column stores, 8 the kept setup's loads.  Never the gathers, the mesh rows, the keep tails or the per-level
+// vectors.
+#ifndef MPAS_NT
+// (measured per group on x1.163842 x 56, DESIGN.md §4q: 2, 4 and 8 shorten the kernels they touch; 1 by itself
+// shortens three of the seven acoustic launches and lengthens four, so it stays out)
+#define MPAS_NT 14
+#endif
+constexpr bool nt_group(int bit) { return (MPAS_NT & bit) != 0; }
+typedef double d2v __attribute__((ext_vector_type(2)));
+// the 16-B pair at p (16-B aligned) as the builtins take it: a 2-double ext vector
+__device__ __forceinline__ double2 ld2_nt(const void* p) {
+    const d2v t = __builtin_nontemporal_load((const d2v*)p);
+    return make_double2(t.x, t.y);
+}
+__device__ __forceinline__ void st2_nt(void* p, double x, double y) {
+    d2v t;
+    t.x = x;
+    t.y = y;
+    __builtin_nontemporal_store(t, (d2v*)p);
+}
+// at_off's streamed twins (below): a value, not a reference
+template <class T>
+__device__ __forceinline__ T ld_off_nt(const T* f, uint32_t off) {
+#if MPAS_BOUNDS
+    return __builtin_nontemporal_load((const T*)bounds_chk(f, (const char*)f + off, sizeof(T)));
+#else
+    return __builtin_nontemporal_load((const MPAS_GLOBAL T*)((const MPAS_GLOBAL char*)(f) + off));
+#endif
+}
+template <class T>
+__device__ __forceinline__ void st_off_nt(T* f, uint32_t off, T v) {
+#if MPAS_BOUNDS
+    __builtin_nontemporal_store(v, (T*)bounds_chk(f, (const char*)f + off, sizeof(T)));
+#else
+    __builtin_nontemporal_store(v, (MPAS_GLOBAL T*)((MPAS_GLOBAL char*)(f) + off));
+#endif
+}
 template <class T>
 __device__ __forceinline__ T& at_off(T* f, uint32_t off) {
 #if MPAS_BOUNDS
@@ -701,6 +744,19 @@ __device__ __forceinline__ T& at_off(T* f, uint32_t off) {
 }
 // level k of column ent of field pointer f (needs LP and k in scope)
 #define colk(f, ent) at_off((f), col_off<LP>((ent), k))
+// the same level loaded / stored with the policy NT (a compile-time bool; false: colk itself)
+template <bool NT, class T>
+__device__ __forceinline__ T ld_off(const T* f, uint32_t off) {
+    if constexpr (NT) return ld_off_nt(f, off);
+    else return at_off(f, off);
+}
+template <bool NT, class T>
+__device__ __forceinline__ void st_off(T* f, uint32_t off, T v) {
+    if constexpr (NT) st_off_nt(f, off, v);
+    else at_off(f, off) = v;
+}
+#define colk_ld(NT, f, ent) ld_off<(NT)>((f), col_off<LP>((ent), k))
+#define colk_st(NT, f, ent, v) st_off<(NT)>((f), col_off<LP>((ent), k), (v))
 
 
 // Two gathered columns, a = level k of column ia of field fa, b = level k of column ib
@@ -720,20 +776,23 @@ __device__ __forceinline__ void swap_halves(double& x, double& y) {
     x = __builtin_bit_cast(double, xi);
     y = __builtin_bit_cast(double, yi);
 }
-template <int LP>
+// (NT: the streamed form, for two columns the launch reads once)
+template <int LP, bool NT = false>
 __device__ __forceinline__ void gather2(const double* fa, int ia, const double* fb, int ib, int k, double& a,
                                         double& b) {
     if constexpr (LP == 64) {
         const bool hi = k >= 32;
         const char* base = hi ? (const char*)fb + (size_t)(uint32_t)ib * 512 : (const char*)fa + (size_t)(uint32_t)ia * 512;
-        const double2 t = *(const double2*)MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16);
+        double2 t;
+        if constexpr (NT) t = ld2_nt(MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16));
+        else t = *(const double2*)MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16);
         double x = t.x, y = t.y;
         swap_halves(x, y);
         a = x;
         b = y;
     } else {
-        a = colk(fa, ia);
-        b = colk(fb, ib);
+        a = colk_ld(NT, fa, ia);
+        b = colk_ld(NT, fb, ib);
     }
 }
 
@@ -814,17 +873,18 @@ __device__ __forceinline__ void put2(double* fa, int ia, double* fb, int ib, int
 // put2 of two whole columns (every level stored: the keep-tail stores, KEEPW): one 16-B store
 // per lane with no mask exchange -- put2's masks, even when all true, cost a permlane of the
 // flags and three divergent store branches (the compiler cannot fold them through the swap)
-template <int LP>
+template <int LP, bool NT = false>
 __device__ __forceinline__ void put2f(double* fa, int ia, double* fb, int ib, int k, double a, double b) {
     if constexpr (LP == 64) {
         double x = a, y = b;
         swap_halves(x, y);
         const bool hi = k >= 32;
         char* base = hi ? (char*)fb + (size_t)(uint32_t)ib * 512 : (char*)fa + (size_t)(uint32_t)ia * 512;
-        *(double2*)MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16) = make_double2(x, y);
+        if constexpr (NT) st2_nt(MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16), x, y);
+        else *(double2*)MPAS_CHK(hi ? fb : fa, base + (k & 31) * 16, 16) = make_double2(x, y);
     } else {
-        colk(fa, ia) = a;
-        colk(fb, ib) = b;
+        colk_st(NT, fa, ia, a);
+        colk_st(NT, fb, ib, b);
     }
 }
 
@@ -983,14 +1043,15 @@ __device__ __forceinline__ void keep_put0(const DevState& S, int f, int kind, in
 #define KEEPW0(v, k0_, kl_) (k == 0 ? (k0_) : KEEPW(v, kl_))
 
 // column read with the level policy: levels outside 0..L read 0.0
-template <int LP>
+// (NT, here and in col_rd2: the streamed form, for a column the launch reads once)
+template <int LP, bool NT = false>
 __device__ __forceinline__ double col_rd(const double* f, int ent, int k, int L) {
-    return ldz(k <= L, at_off(f, col_off<LP>(ent, k)));
+    return ldz(k <= L, ld_off<NT>(f, col_off<LP>(ent, k)));
 }
 // col_rd of two fields of one column (gather2)
-template <int LP>
+template <int LP, bool NT = false>
 __device__ __forceinline__ void col_rd2(const double* f, const double* g, int ent, int k, int L, double& a, double& b) {
-    gather2<LP>(f, ent, g, ent, k, a, b);
+    gather2<LP, NT>(f, ent, g, ent, k, a, b);
     a = ldz(k <= L, a);
     b = ldz(k <= L, b);
 }
